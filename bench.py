@@ -5,8 +5,8 @@
 
 A "step" = one pass of the hot path over one batch of synthetic queries. The headline (`metric`/`value`) is BASELINE
 config 2 — 10M-doc Zipf collection (V=100K, 32 tokens/doc, seed 2), a batch of 10 000 3-term conjunctive queries (ranks
-log-uniform [8,2000]), Topster 250 (per_page 100), sort [_text_match desc, points desc]. With the default
-`--workload all` the same JSON line also carries `vector` (config 3: 10M x 768 fp32, batched exact inner-product
+log-uniform [8,2000]), Topster 250 (per_page 100), sort [_text_match desc, points desc]. A plain run times only that; with
+`--full` (and the default `--workload all`) the same JSON line also carries `vector` (config 3: 10M x 768 fp32, batched exact inner-product
 top-100) and `hybrid` (config 4: keyword + vector + reciprocal-rank fusion) sub-objects, each timed the same way, each with
 its own parity object checked at FULL size against the oracle.
 
@@ -43,6 +43,7 @@ MFMA_BF16_ISSUE_CEILING_TF = 1580.0   # measured: vec_hscan_kernel<4> with only 
 FETCH_SIZE = 100
 K_TOPSTER = 250
 PROFILE_ROUND = "r06"
+DUMP_QUERIES = 1024          # --dump-outputs: queries of the batch whose hit lists are written (seeded sample, the same every run)
 
 
 def parse():
@@ -77,7 +78,21 @@ def parse():
                     help="N>1: shards (default, BASELINE config 5) = the collection cut into N doc ranges, every GPU scores the whole batch on its "
                          "shard, all-gather of the per-GPU top-K + exact device merge (strong scaling); replicas = every GPU holds the collection, "
                          "the global batch (N x per-GPU batch) is sharded across the GPUs (weak scaling)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: with --workload all also the vector and hybrid configs; the CPU baselines and the parity checks "
+                         "against the oracle; the secondary legs (concurrency, uncached terms, vector sweeps and variants, HNSW, general kernels); the "
+                         "headline's other forms (all arrays, pinned host arrays, two callers, device-only) and the keyword roofline they feed; N>1: the "
+                         "unsharded twin, its in-run equality checks and the replicas forms. Without it a run sets up, warms up, times the headline's "
+                         "steps and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's timed path delivered in its last step as DIR/<name>.npy (float64, or "
+                         "float32 for fp32 outputs); per-hit arrays of a fixed sample of %d queries" % DUMP_QUERIES)
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload in ("kwgeneral", "hnsw"):
+        ap.error("--dump-outputs writes the outputs of the headline configs (--workload all, keyword, vector or hybrid)")
+    if not a.full:
+        a.no_cpu_baseline = a.no_extras = True
+    return a
 
 
 def dist_setup(n_gpus):
@@ -228,6 +243,45 @@ def device_hits(torch, n_q, ks):
     return d, h
 
 
+# ---------------------------------------------------------------- --dump-outputs
+def dump_rows(n_q):
+    """the queries whose hit lists are written: a seeded sample of the batch, ascending"""
+    return np.sort(np.random.default_rng(20).choice(n_q, size=min(n_q, DUMP_QUERIES), replace=False))
+
+
+def hit_rows(n_hits, rows, **per_hit):
+    """per-hit arrays [n_q, k, ...] -> their `rows`; the slots past a query's n_hits are not part of its result and are written as 0 (keys: -1)"""
+    nh = np.asarray(n_hits).astype(np.int64)[rows]
+    out = {}
+    for name, a in per_hit.items():
+        a = np.asarray(a)[rows]
+        if a.dtype == np.uint64:
+            a = a.view(np.int64)
+        live = (np.arange(a.shape[1])[None, :] < nh[:, None]).reshape(a.shape[:2] + (1,) * (a.ndim - 2))
+        out[name] = np.where(live, a, -1 if name == "keys" else 0)
+    return out
+
+
+def split64(a):
+    """int64 words (packed scores exceed the 2^53 that float64 holds exactly) -> (signed high 32 bits, low 32 bits)"""
+    a = np.asarray(a).astype(np.int64)
+    return a >> 32, a & 0xFFFFFFFF
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy per array: float32 stays float32, every other array becomes float64, which must hold it exactly"""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        f = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        assert a.dtype.kind == "f" or np.array_equal(f.astype(a.dtype), a), "%s does not fit float64 exactly" % name
+        np.save(os.path.join(dirname, name + ".npy"), f)
+        total += f.nbytes
+    assert total <= 64 << 20, "--dump-outputs wrote %d bytes (limit 64 MB)" % total
+    return total
+
+
 def cpu_quota_cpus():
     """CPUs the container may use (cgroup v2 cpu.max), None = unlimited: the cpu_baseline legs start one thread per visible core, the quota decides how many run"""
     try:
@@ -279,6 +333,8 @@ class Bench:
         self.csr = None
         self.exact = None           # exact k-NN of the first queries by the oracle's chunked flat scan (vector + hybrid parity)
         self.extras = not args.no_extras and world == 1
+        self.head = "keyword" if args.workload == "all" else args.workload      # the leg whose figure heads the line (and whose outputs --dump-outputs writes)
+        self.dump = None
         # N > 1, shards: the exchange runs behind the C-ABI (tsgpu_group, rank form): RCCL collectives on the context's stream + the library's
         # merge kernels (rank 0's ncclUniqueId travels through torch.distributed). Under TSGPU_DIST_BACKEND=gloo (rehearsal: the ranks share
         # one GPU) the same group runs over its HOST transport (the callbacks = torch.distributed on host memory). If the group cannot be
@@ -292,6 +348,19 @@ class Bench:
             else:
                 self.exchange = ("tsgpu_group (C-ABI, rank form, HOST transport over torch.distributed/%s callbacks): all-gather of the shards' bounds, all-to-all of the bound-pruned "
                                  "query slices + slice merge, staged through pinned host memory; k-NN: one all-gather + vec_group_merge_kernel" % os.environ.get("TSGPU_DIST_BACKEND", "nccl"))
+
+    def set_dump(self, n_hits, per_query, per_hit):
+        """--dump-outputs of the head leg: its per-query arrays for the whole batch, its per-hit arrays for the dump_rows() sample; the
+        64-bit score words go out as two exact halves (<name>_hi, <name>_lo)"""
+        rows = dump_rows(len(n_hits))
+        d = {"sample_rows": rows, "n_hits": np.array(n_hits)}
+        d.update((k, np.array(v)) for k, v in per_query.items())
+        for name, a in hit_rows(n_hits, rows, **per_hit).items():
+            if name in ("scores", "text_match"):
+                d[name + "_hi"], d[name + "_lo"] = split64(a)
+            else:
+                d[name] = a
+        self.dump = d
 
     def all_ranks_or_die(self, ok, what, err):
         """every rank learns whether `what` succeeded everywhere; if not, every rank raises (no rank is left inside a collective, and no
@@ -363,6 +432,7 @@ class Bench:
         self.csr = load(self.g, (self.lo, self.hi) if self.sharded else None)
         if self.sharded:
             self.g.set_option("doc_range_lo", int(self.lo)); self.g.set_option("doc_range_hi", int(self.hi))      # the seq_ids this shard owns (q = * ranks only those)
+        if self.sharded and self.args.full:
             # every rank also holds the WHOLE collection (6 GB): rank 0 checks the merged shard results against it, and all ranks run the
             # second multi-GPU form (replicas) on it
             self.twin = self.T.GpuIndex(self.torch.cuda.current_device())
@@ -410,7 +480,7 @@ class Bench:
         from typesense_amd import _lib as B
         t0 = time.time()
         self.load_vectors(self.g, 1, B.METRIC_IP, self.lo, self.hi)
-        if self.sharded and self.rank == 0:          # the unsharded matrix, for the in-bench equality check
+        if self.twin is not None and self.rank == 0:          # the unsharded matrix, for the in-bench equality check
             self.load_vectors(self.twin, 1, B.METRIC_IP, 0, self.n_docs)
         return time.time() - t0
 
@@ -470,9 +540,15 @@ class Bench:
             def step_host_all():
                 g.keyword_search_batch_raw(arr, n_q, hhs_all)
                 return hh
-            el_all, _lat_all, _ = timed(step_host_all, max(args.steps // 2, 3), min(args.warmup, 2), world)
-            self.host_all_arrays_ms = 1e3 * el_all / max(args.steps // 2, 3)
+            if args.full:
+                el_all, _lat_all, _ = timed(step_host_all, max(args.steps // 2, 3), min(args.warmup, 2), world)
+                self.host_all_arrays_ms = 1e3 * el_all / max(args.steps // 2, 3)
             el_host, lat_host, _ = timed(step_host, args.steps, args.warmup, world)
+            if self.head == "keyword" and args.dump_outputs:        # (before the legs below write into the same arrays)
+                self.set_dump(hh.n_hits, dict(num_matched=hh.num_matched, status=hh.status, search_cutoff=hh.search_cutoff),
+                              dict(keys=hh.keys, scores=hh.scores, match_score_index=hh.match_score_index))
+            if not args.full:
+                return dict(elapsed=el_host, lat=lat_host, n_q=n_q, n_postings=int(self.csr["n_postings"]), nonempty=int((hh.n_hits > 0).sum()))
             # the headline's batch delivered to PINNED host arrays (hipHostMalloc'ed once by the caller, e.g. the shim's reusable result arrays): the copy-out is a
             # plain DMA instead of the runtime's staged copy to pageable memory — reported next to the headline (`value_host_pinned`)
             try:
@@ -540,6 +616,8 @@ class Bench:
                     elapsed, lat, _ = timed(step_own_slice, args.steps, args.warmup, world, after)
                 finally:
                     self.group.set_option("kw_own_slice_only", 0)
+                if not args.full and not (self.head == "keyword" and args.dump_outputs):
+                    return dict(elapsed=elapsed, lat=lat, n_q=n_q, n_postings=int(self.csr["n_postings"]), nonempty=None)
                 out = step()
                 mine = slice(q0, q1)
                 self.own_slice_ok = bool(q1 <= q0 or (torch.equal(ph["n_hits"][mine].to(torch.int64), out[2][mine].to(torch.int64).cpu()) and
@@ -564,7 +642,7 @@ class Bench:
         res = dict(elapsed=elapsed, lat=lat, touched=touched, kern_ms=float(np.mean(kern_ms)), merge_ms=float(np.mean(merge_ms)), find_ms=float(np.mean(find_ms)),
                    alg_bytes=float(np.mean(alg_bytes)), n_q=n_q, n_postings=int(self.csr["n_postings"]), elapsed_dev=elapsed_dev, lat_dev=lat_dev,
                    host_all_arrays_ms=getattr(self, "host_all_arrays_ms", None), two_callers=getattr(self, "two_callers", None), host_pinned=getattr(self, "host_pinned", None))
-        if self.group is not None:
+        if self.group is not None and args.full:
             # the bound-pruned exchange against the full top-k exchange (untimed): same merged result, fewer bytes
             gt = self.group.timings()
             self.group.set_option("kw_exchange_pruned", 0)
@@ -587,6 +665,11 @@ class Bench:
         n_hits = out[2].cpu().numpy()
         num_matched = out[3].cpu().numpy()
         res["nonempty"] = int((n_hits > 0).sum())
+        if self.group is not None and self.head == "keyword" and args.dump_outputs:
+            # N>1: the merged result of the whole batch (every rank holds it; the timed steps delivered it to the ranks' hosts slice by slice)
+            self.set_dump(n_hits, dict(num_matched=num_matched), dict(keys=keys[:, :FETCH_SIZE], scores=scores[:, :FETCH_SIZE]))
+        if not args.full:
+            return res
 
         if self.sharded and self.rank == 0:
             # in-bench equality: the merged result of the sharded collection == the unsharded twin's result (same corpus, same queries)
@@ -1352,14 +1435,16 @@ class Bench:
         res.update(prefilter=int(self.opts.get("vec_prefilter", 1)), fallbacks=g.counter("vec_prefilter_fallbacks") - f0,
                    overflow_rounds=g.counter("vec_overflow_rounds") - o0)
         d_gpu, l_gpu, c_gpu = out[0].cpu().numpy(), out[1].cpu().numpy(), out[2].cpu().numpy()
+        if self.head == "vector" and args.dump_outputs:
+            self.set_dump(c_gpu, {}, dict(distances=d_gpu, labels=l_gpu))
 
-        if self.sharded and self.rank == 0:
+        if self.twin is not None and self.rank == 0:
             m = min(n_q, 16)
             td, tl, tc = self.twin.vec_knn_batch(1, Q[:m].cpu().numpy(), k)
             bad = sum(1 for i in range(m) if not (np.array_equal(l_gpu[i], tl[i].astype(np.int64)) and np.array_equal(d_gpu[i].view(np.uint32), td[i].view(np.uint32))))
             res["shard_parity"] = {"checked": m, "mismatches": bad, "against": "the unsharded 10M x %d matrix on rank 0 (labels + distance bits)" % dim}
 
-        if world == 1 and res["prefilter"]:
+        if world == 1 and res["prefilter"] and args.full:
             # parity leg 1 (GPU vs GPU): the bf16 bracket path must return exactly what the fp32 scan of EVERY row returns
             m = min(n_q, 16)
             g.set_option("vec_prefilter", 0)
@@ -1662,6 +1747,8 @@ class Bench:
         qtok = synth.keyword_queries(n_q, 3, 8, 2000, seed=5 + self.qseed)
         qs = [self.T.KwQuery(qtok[i], sort=self.sort, topster_size=K_TOPSTER) for i in range(n_q)]
         arr = self.kw_query_array(qtok)
+        if not hasattr(self, "Q"):      # (the vector leg did not run: --workload hybrid without --full)
+            self.Q = synth.random_vectors(n_q, args.dim, seed=4 + self.qseed, device="cuda")
         Qh = self.Q[:n_q].cpu().numpy()
         if not self.sharded:                      # 1 GPU, or replicas: every rank fuses its own slice of the global batch
             def step():
@@ -1684,7 +1771,10 @@ class Bench:
         res = dict(elapsed=elapsed, steps=steps, lat=lat, n_q=n_q)
         if out is not None:
             res["fused_hits"] = int(out.n_hits.sum())
-        if self.sharded and self.rank == 0:
+            if self.head == "hybrid" and args.dump_outputs:
+                self.set_dump(out.n_hits, dict(num_matched=out.num_matched, status=out.status),
+                              dict(keys=out.keys, scores=out.scores, text_match=out.text_match, vector_distance=out.vector_distance))
+        if self.twin is not None and self.rank == 0:
             m = min(n_q, 16)
             th = self.twin.hybrid_search_batch(qs[:m], 1, Qh[:m], k=k, fetch_size=100, alpha=0.3, k_stride=K_TOPSTER)
             bad = 0
@@ -1944,6 +2034,8 @@ def main():
     barrier(world)
 
     wl = args.workload
+    if wl == "all" and not args.full:
+        wl = "keyword"          # a plain run times the headline's leg only
     bn = Bench(args, rank, world)
     out = {}
     build_s = {}
@@ -1953,7 +2045,7 @@ def main():
         build_s["vector_index"] = bn.build_vectors()
     if wl in ("all", "keyword"):
         out["keyword"] = bn.run_keyword()
-    if wl in ("all", "vector", "hybrid"):
+    if wl in ("all", "vector") or (wl == "hybrid" and args.full):
         out["vector"] = bn.run_vector()
     if wl in ("all", "hybrid"):
         out["hybrid"] = bn.run_hybrid()
@@ -1980,6 +2072,8 @@ def main():
         print(json.dumps({"metric": "queries/sec, general keyword kernels at %d docs" % args.n_docs, "n_gpus": world, "data": "synthetic", "general_kernels": out.get("keyword_general"),
                           "index_build_s": build_s}))
         return
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, bn.dump)
 
     sharded = world > 1 and args.dist_mode == "shards"
     mult = world if (world > 1 and not sharded) else 1            # replicas: the global batch is world x the per-GPU batch
@@ -2000,7 +2094,6 @@ def main():
     if "keyword" in out:
         r = out["keyword"]
         qps = mult * r["n_q"] * args.steps / r["elapsed"]
-        achieved = r["alg_bytes"] / (r["kern_ms"] * 1e-3) / 1e9 if r["kern_ms"] > 0 else 0.0
         kw = line_common(args, world, qps, r["elapsed"], args.steps, r["lat"])
         kw["config"] = {"workload": "BASELINE config 2: %d-doc Zipf(1.0) text, V=%d, %d tokens/doc, %d postings/shard; %d queries/step, 3 distinct "
                                     "terms ranks log-uniform [8,2000], Topster 250, sort [_text_match desc, points desc], num_typos=0, prefix=false"
@@ -2031,73 +2124,75 @@ def main():
         if r.get("elapsed_dev"):
             kw["value_device_only"] = mult * r["n_q"] * args.steps / r["elapsed_dev"]       # outputs left in HBM: the single-launch form the roofline / rocprof durations refer to
             kw["ms_per_step_device_only"] = 1e3 * r["elapsed_dev"] / args.steps
-        find_rx, score_rx = r"kw_find2_kernel<3(, false)?>|kw_search_kernel<3, 512, true, true>", r"kw_score_kernel<3, 512, false, false, true>"      # (not the COUNT instantiation's one launch)
-        # (max over the dispatches = the full 10 000-query launch: the profiled command also runs the host-delivery leg, whose slices
-        #  are smaller launches of the same kernels and would dilute an average)
-        traffic = pmc_traffic([find_rx, score_rx], ["pmc_kw_fetch.txt", "pmc_kw_s5_fetch.txt"], field="max")
-# What bounds the kernel. SURVEY 8(d)'s figure — algorithmic bytes / kernel time / 8 TB/s — is 1.3-1.4: above 1, because the
-        # find kernel SKIPS (only the shortest list is scanned; the others are met per overlapping run or per candidate) — it is kept as
-        # `algorithmic_frac`, it bounds nothing. The line's `frac` is the utilisation of the find kernel's busiest issue port, the CU's one scalar
-        # unit (SQ_INSTS_SALU of the round's committed --pmc pass / (live kernel cycles x 256 CUs)); `touched_*` = the bytes the kernels REQUEST, counted
-        # by the find kernel itself (kw_count_touched instantiation, one extra untimed step of the same batch); `traffic` = what left L2 (FETCH_SIZE);
-        # `l2_refetch` = traffic / the bytes the batch's DISTINCT lists occupy (ids + block records + directories + offsets).
-        roof = {"algorithmic_achieved_GBs": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "kernel": "kw_find2_kernel<3> (two driver blocks per iteration) + kw_score_kernel<512> (the two halves of the intersect+score+select step, "
-                          "launched back to back; kernel_ms spans both)", "kernel_ms": r["kern_ms"], "merge_kernel_ms": r["merge_ms"],
-                "algorithmic_bytes_per_launch": r["alg_bytes"],
-                "note": "bound = the find kernel's busiest issue port (scalar unit: loop control, exec-mask bookkeeping, v_readlane window reads, spilled SGPRs) with "
-                        "dependent LDS / L2 latency behind it; algorithmic_frac (SURVEY 8(d): 4*sum|L_t| + offsets + sort keys over kernel time over 8 TB/s) exceeds 1 "
-                        "because the kernel skips — it is not a distance to any limit; touched_frac / traffic_frac are the byte rates that do exist."}
-        if r["find_ms"] > 0:
-            fa = r["alg_bytes"] / (r["find_ms"] * 1e-3) / 1e9
-            roof["find_kernel_ms"] = r["find_ms"]
-            roof["find_kernel_alone_algorithmic_frac"] = fa / HBM_PEAK_GBS
-        tch = r.get("touched")
-        if tch and r["kern_ms"] > 0:
-            tb = tch["find_requested_bytes"] + tch["score_requested_bytes"]
-            fp = tch["footprint"]
-            uniq = fp["ids_bytes"] + fp["block_metadata_bytes"] + fp["directory_bytes"] + fp["payload_bytes"]
-            roof["touched_bytes_per_launch"] = tb
-            roof["touched_frac"] = tb / (r["kern_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof["touched"] = {k: tch[k] for k in ("find_requested_bytes", "find_driver_ids", "find_metadata", "find_tile_dma", "find_probes", "find_records",
-                                                  "find_work_items", "find_hit_records", "score_requested_bytes")}
-            roof["touched"]["note"] = ("counted by kw_find2_kernel<3, COUNT=true> itself (every lane adds the width of its own loads / LDS-DMA words / stores; one untimed step "
-                                       "of the same batch); score_requested_bytes = hit records x the score kernel's fixed request sizes")
-            roof["unique_list_bytes"] = uniq
-            roof["unique_lists"] = fp
-            roof["requested_over_unique"] = tb / uniq if uniq else None
-            if traffic:
-                roof["l2_refetch"] = traffic / uniq if uniq else None
-                roof["l2_refetch_x2"] = 2.0 * traffic / uniq if uniq else None
-                roof["l2_hit_rate_of_requests"] = max(0.0, 1.0 - traffic / tb) if tb else None
-        if traffic and r["kern_ms"] > 0:
-            roof["traffic_frac"] = traffic / (r["kern_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof["traffic_frac_x2"] = 2.0 * roof["traffic_frac"]      # upper bound if every read were a wide one (FETCH_SIZE halves those on gfx950)
-            roof["algorithmic_over_fetched"] = r["alg_bytes"] / traffic
-        sq1 = ["pmc_kw_sq1.txt", "pmc_kw_s5_sq1.txt"]
-        valu = pmc_counter(find_rx, sq1, "SQ_INSTS_VALU", field="max")
-        salu = pmc_counter(find_rx, sq1, "SQ_INSTS_SALU", field="max")
-        lds = pmc_counter(find_rx, sq1, "SQ_INSTS_LDS", field="max")
-        cyc = (r["find_ms"] or r["kern_ms"]) * 1e-3 * 2.4e9
-        # THE ROOFLINE (HBM-bound integer path): achieved = the algorithmic bytes of the launch / the live duration of the two kernels, peak = 8 TB/s.
-        # The fraction exceeds 1 because the find kernel SKIPS (leap-frog: only the shortest list is scanned, the others are met per overlapping run or per
-        # candidate) — SURVEY 8(d) says so in advance; `traffic` (FETCH_SIZE) and `touched_*` (counted by the kernel itself) are the byte rates that exist.
-        roof.update({"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "note": "frac > 1 = leap-frog skipping (algorithmic bytes 4*sum|L_t| + offsets + sort keys are not all fetched), not a distance to a limit. What the "
-                             "find kernel waits for is the NUMBER of dependent steps per candidate (block search, four LDS metadata reads, nine dependent LDS reads, "
-                             "compaction barrier, one directory load per survivor): round 6 halved its scalar instructions (slower), cut its vector instructions 5 % (-1 %), "
-                             "made the probed directories L2-resident (< 1 %), round 5 cut its tile bytes 30 % (0) — profiles/r06/exp_find2_valu.txt; issue_util gives the ports."})
-        if valu and salu and cyc > 0:
-            # issue capacity per CU and cycle: a wave64 VALU instruction holds one of the CU's four 16-lane SIMDs for 4 cycles -> 1 VALU wave-instruction per CU
-            # and cycle; ONE scalar unit -> 1 SALU instruction. Kernel cycles = its live HIP-event duration at the 2.4 GHz peak clock. The counters come from
-            # the committed --pmc pass; `pmc_of_these_sources` says whether that pass profiled the kernel sources this run was built from.
-            meta = _pmc_meta(sq1[0])
-            cur = kernel_src_sha16()
-            roof["issue_util"] = {"valu": valu / (cyc * 256), "salu": salu / (cyc * 256), "insts_valu": valu, "insts_salu": salu, "insts_lds": lds,
-                                  "pmc_file": os.path.relpath(_profile(sq1[0]) or "profiles/", ROOT), "pmc_kernel_src_sha16": (meta or {}).get("kernel_src_sha16"),
-                                  "kernel_src_sha16": cur, "pmc_of_these_sources": bool(meta) and meta.get("kernel_src_sha16") == cur,
-                                  "note": "wave-instructions of the find kernel (rocprofv3 --pmc, own pass) / (live kernel cycles x 256 CUs x 1 per cycle); no port is saturated"}
-        kw["roofline"] = roof
+        if args.full:      # (the keyword roofline is computed from the device-only and byte-counting legs)
+            achieved = r["alg_bytes"] / (r["kern_ms"] * 1e-3) / 1e9 if r["kern_ms"] > 0 else 0.0
+            find_rx, score_rx = r"kw_find2_kernel<3(, false)?>|kw_search_kernel<3, 512, true, true>", r"kw_score_kernel<3, 512, false, false, true>"      # (not the COUNT instantiation's one launch)
+            # (max over the dispatches = the full 10 000-query launch: the profiled command also runs the host-delivery leg, whose slices
+            #  are smaller launches of the same kernels and would dilute an average)
+            traffic = pmc_traffic([find_rx, score_rx], ["pmc_kw_fetch.txt", "pmc_kw_s5_fetch.txt"], field="max")
+            # What bounds the kernel. SURVEY 8(d)'s figure — algorithmic bytes / kernel time / 8 TB/s — is 1.3-1.4: above 1, because the
+            # find kernel SKIPS (only the shortest list is scanned; the others are met per overlapping run or per candidate) — it is kept as
+            # `algorithmic_frac`, it bounds nothing. The line's `frac` is the utilisation of the find kernel's busiest issue port, the CU's one scalar
+            # unit (SQ_INSTS_SALU of the round's committed --pmc pass / (live kernel cycles x 256 CUs)); `touched_*` = the bytes the kernels REQUEST, counted
+            # by the find kernel itself (kw_count_touched instantiation, one extra untimed step of the same batch); `traffic` = what left L2 (FETCH_SIZE);
+            # `l2_refetch` = traffic / the bytes the batch's DISTINCT lists occupy (ids + block records + directories + offsets).
+            roof = {"algorithmic_achieved_GBs": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "kernel": "kw_find2_kernel<3> (two driver blocks per iteration) + kw_score_kernel<512> (the two halves of the intersect+score+select step, "
+                              "launched back to back; kernel_ms spans both)", "kernel_ms": r["kern_ms"], "merge_kernel_ms": r["merge_ms"],
+                    "algorithmic_bytes_per_launch": r["alg_bytes"],
+                    "note": "bound = the find kernel's busiest issue port (scalar unit: loop control, exec-mask bookkeeping, v_readlane window reads, spilled SGPRs) with "
+                            "dependent LDS / L2 latency behind it; algorithmic_frac (SURVEY 8(d): 4*sum|L_t| + offsets + sort keys over kernel time over 8 TB/s) exceeds 1 "
+                            "because the kernel skips — it is not a distance to any limit; touched_frac / traffic_frac are the byte rates that do exist."}
+            if r["find_ms"] > 0:
+                fa = r["alg_bytes"] / (r["find_ms"] * 1e-3) / 1e9
+                roof["find_kernel_ms"] = r["find_ms"]
+                roof["find_kernel_alone_algorithmic_frac"] = fa / HBM_PEAK_GBS
+            tch = r.get("touched")
+            if tch and r["kern_ms"] > 0:
+                tb = tch["find_requested_bytes"] + tch["score_requested_bytes"]
+                fp = tch["footprint"]
+                uniq = fp["ids_bytes"] + fp["block_metadata_bytes"] + fp["directory_bytes"] + fp["payload_bytes"]
+                roof["touched_bytes_per_launch"] = tb
+                roof["touched_frac"] = tb / (r["kern_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof["touched"] = {k: tch[k] for k in ("find_requested_bytes", "find_driver_ids", "find_metadata", "find_tile_dma", "find_probes", "find_records",
+                                                      "find_work_items", "find_hit_records", "score_requested_bytes")}
+                roof["touched"]["note"] = ("counted by kw_find2_kernel<3, COUNT=true> itself (every lane adds the width of its own loads / LDS-DMA words / stores; one untimed step "
+                                           "of the same batch); score_requested_bytes = hit records x the score kernel's fixed request sizes")
+                roof["unique_list_bytes"] = uniq
+                roof["unique_lists"] = fp
+                roof["requested_over_unique"] = tb / uniq if uniq else None
+                if traffic:
+                    roof["l2_refetch"] = traffic / uniq if uniq else None
+                    roof["l2_refetch_x2"] = 2.0 * traffic / uniq if uniq else None
+                    roof["l2_hit_rate_of_requests"] = max(0.0, 1.0 - traffic / tb) if tb else None
+            if traffic and r["kern_ms"] > 0:
+                roof["traffic_frac"] = traffic / (r["kern_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof["traffic_frac_x2"] = 2.0 * roof["traffic_frac"]      # upper bound if every read were a wide one (FETCH_SIZE halves those on gfx950)
+                roof["algorithmic_over_fetched"] = r["alg_bytes"] / traffic
+            sq1 = ["pmc_kw_sq1.txt", "pmc_kw_s5_sq1.txt"]
+            valu = pmc_counter(find_rx, sq1, "SQ_INSTS_VALU", field="max")
+            salu = pmc_counter(find_rx, sq1, "SQ_INSTS_SALU", field="max")
+            lds = pmc_counter(find_rx, sq1, "SQ_INSTS_LDS", field="max")
+            cyc = (r["find_ms"] or r["kern_ms"]) * 1e-3 * 2.4e9
+            # THE ROOFLINE (HBM-bound integer path): achieved = the algorithmic bytes of the launch / the live duration of the two kernels, peak = 8 TB/s.
+            # The fraction exceeds 1 because the find kernel SKIPS (leap-frog: only the shortest list is scanned, the others are met per overlapping run or per
+            # candidate) — SURVEY 8(d) says so in advance; `traffic` (FETCH_SIZE) and `touched_*` (counted by the kernel itself) are the byte rates that exist.
+            roof.update({"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                         "note": "frac > 1 = leap-frog skipping (algorithmic bytes 4*sum|L_t| + offsets + sort keys are not all fetched), not a distance to a limit. What the "
+                                 "find kernel waits for is the NUMBER of dependent steps per candidate (block search, four LDS metadata reads, nine dependent LDS reads, "
+                                 "compaction barrier, one directory load per survivor): round 6 halved its scalar instructions (slower), cut its vector instructions 5 % (-1 %), "
+                                 "made the probed directories L2-resident (< 1 %), round 5 cut its tile bytes 30 % (0) — profiles/r06/exp_find2_valu.txt; issue_util gives the ports."})
+            if valu and salu and cyc > 0:
+                # issue capacity per CU and cycle: a wave64 VALU instruction holds one of the CU's four 16-lane SIMDs for 4 cycles -> 1 VALU wave-instruction per CU
+                # and cycle; ONE scalar unit -> 1 SALU instruction. Kernel cycles = its live HIP-event duration at the 2.4 GHz peak clock. The counters come from
+                # the committed --pmc pass; `pmc_of_these_sources` says whether that pass profiled the kernel sources this run was built from.
+                meta = _pmc_meta(sq1[0])
+                cur = kernel_src_sha16()
+                roof["issue_util"] = {"valu": valu / (cyc * 256), "salu": salu / (cyc * 256), "insts_valu": valu, "insts_salu": salu, "insts_lds": lds,
+                                      "pmc_file": os.path.relpath(_profile(sq1[0]) or "profiles/", ROOT), "pmc_kernel_src_sha16": (meta or {}).get("kernel_src_sha16"),
+                                      "kernel_src_sha16": cur, "pmc_of_these_sources": bool(meta) and meta.get("kernel_src_sha16") == cur,
+                                      "note": "wave-instructions of the find kernel (rocprofv3 --pmc, own pass) / (live kernel cycles x 256 CUs x 1 per cycle); no port is saturated"}
+            kw["roofline"] = roof
         for key in ("concurrency", "uncached", "shard_parity", "replicas", "replicas_strong", "exchange_check", "candidate_combinations_sharded", "wildcard_sharded", "group_by_sharded"):
             if key in r:
                 kw[key] = r[key]

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,3 +55,28 @@ def test_compact_line_sheds_optional_objects_before_it_exceeds_the_budget():
     line = bench.compact_line(full, "x.json")
     assert len(json.dumps(line)) <= bench.COMPACT_LIMIT
     assert "concurrency" not in line and line["roofline"]["frac"] and line["cpu_baseline"]["value"] and line["vector"]["value"]
+
+
+def test_dump_outputs_are_exact_and_mask_the_slots_past_n_hits(tmp_path):
+    """--dump-outputs helpers: a fixed sample of queries, slots past n_hits masked, 64-bit score words exact through two float64 halves"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    n_q, k = 3000, 8
+    n_hits = rng.integers(0, k + 1, n_q).astype(np.uint32)
+    keys = rng.integers(0, 10_000_000, (n_q, k)).astype(np.uint64)
+    scores = rng.integers(-2 ** 63, 2 ** 63 - 1, (n_q, k, 3), dtype=np.int64)
+    rows = bench.dump_rows(n_q)
+    assert rows.size == bench.DUMP_QUERIES and np.array_equal(rows, bench.dump_rows(n_q)) and (np.diff(rows) > 0).all()
+    h = bench.hit_rows(n_hits, rows, keys=keys, scores=scores)
+    hi, lo = bench.split64(h["scores"])
+    bench.write_outputs(str(tmp_path), dict(n_hits=n_hits, keys=h["keys"], scores_hi=hi, scores_lo=lo, dist=np.ones(4, np.float32)))
+    back = {n: np.load(tmp_path / (n + ".npy")) for n in ("n_hits", "keys", "scores_hi", "scores_lo", "dist")}
+    assert back["dist"].dtype == np.float32 and all(back[n].dtype == np.float64 for n in ("n_hits", "keys", "scores_hi", "scores_lo"))
+    whole = (back["scores_hi"].astype(np.int64) << 32) | back["scores_lo"].astype(np.int64)
+    for j, q in enumerate(rows):
+        n = int(n_hits[q])
+        assert np.array_equal(back["keys"][j, :n].astype(np.uint64), keys[q, :n]) and (back["keys"][j, n:] == -1).all()
+        assert np.array_equal(whole[j, :n], scores[q, :n]) and (whole[j, n:] == 0).all()
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path), dict(too_wide=scores))          # float64 cannot hold these words: refused, not rounded

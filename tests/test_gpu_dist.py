@@ -22,7 +22,7 @@ def test_n_rank_shards_equal_unsharded_collection(world):
     env = dict(os.environ, TSGPU_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29613 + world),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--n-docs", "2000000", "--batch", "1000", "--vec-batch", "64",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,9 +1,9 @@
 # usage: bash tools/experiments/run_benchkw.sh <tag> [extra bench.py args]: the keyword leg of bench.py (parity + cpu_baseline included), key numbers printed
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/f2
+O=${TMPDIR:-/tmp}/benchkw; mkdir -p $O
 tag=$1; shift
-python bench.py --workload keyword --steps 20 --warmup 5 "$@" > gpurun_out/f2/bench_$tag.json 2> gpurun_out/f2/bench_$tag.err
-python - gpurun_out/f2/bench_$tag.json <<'PY'
+python bench.py --full --workload keyword --steps 20 --warmup 5 "$@" > $O/bench_$tag.json 2> $O/bench_$tag.err
+python - $O/bench_$tag.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -6,7 +6,7 @@ IFS=';' read -ra SETS <<< "$2"
 i=0
 for set in "${SETS[@]}"; do
   OPTS=""; if [ "$set" != "none" ]; then for o in $set; do OPTS="$OPTS --opt $o"; done; fi
-  timeout 900 python bench.py --workload keyword --no-cpu-baseline --steps 5 --warmup 2 $OPTS --detail-out $O/detail_$i.json > $O/kw_$i.json 2> $O/kw_$i.err
+  timeout 900 python bench.py --full --workload keyword --no-cpu-baseline --steps 5 --warmup 2 $OPTS --detail-out $O/detail_$i.json > $O/kw_$i.json 2> $O/kw_$i.err
   python - $O/detail_$i.json "$set" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); c = d.get("concurrency") or {}

@@ -23,7 +23,7 @@ PY
 done
 for v in $2; do
   L=""; if [ "$v" != "-" ]; then L=$PWD/typesense_amd/variants/libtsgpu_$v.so; fi
-  TSGPU_LIB=$L timeout 600 python bench.py --workload keyword --no-extras --no-cpu-baseline --steps 10 --warmup 3 --detail-out $O/detail_$v.json > $O/kw_$v.json 2> $O/kw_$v.err
+  TSGPU_LIB=$L timeout 600 python bench.py --full --workload keyword --no-extras --no-cpu-baseline --steps 10 --warmup 3 --detail-out $O/detail_$v.json > $O/kw_$v.json 2> $O/kw_$v.err
   python - $O/detail_$v.json $v <<'PY'
 import json, sys
 try:

@@ -2,6 +2,7 @@
 # usage: bash tools/experiments/run_r06_b.sh "<variants, '-' = default lib>" "<option sets: name=v,name=v ... ; '-' = defaults>" <tag> ["pytest -k expression" | skip]
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
+ROOT=$PWD
 O=gpurun_out/r06_$3; mkdir -p $O
 if [ "${4:-skip}" != "skip" ]; then
   ( time timeout 1200 python -m pytest tests -m gpu -x -q -k "$4" ) > $O/pytest_gpu.txt 2>&1; tail -8 $O/pytest_gpu.txt
@@ -11,7 +12,7 @@ for v in $1; do
   for os in $2; do
     OPTS=""; if [ "$os" != "-" ]; then for o in ${os//,/ }; do OPTS="$OPTS --opt $o"; done; fi
     tag="${v}_${os//[=,]/_}"
-    ( cd /tmp && TSGPU_LIB=$L timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/trace_$tag -- python $GRAFT_REPO_ROOT/bench.py --workload keyword --no-extras --no-cpu-baseline --steps 10 --warmup 3 $OPTS --detail-out $GRAFT_REPO_ROOT/$O/detail_$tag.json > $GRAFT_REPO_ROOT/$O/kw_$tag.json 2> $GRAFT_REPO_ROOT/$O/kw_$tag.err )
+    ( cd /tmp && TSGPU_LIB=$L timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$O/trace_$tag -- python $ROOT/bench.py --full --workload keyword --no-extras --no-cpu-baseline --steps 10 --warmup 3 $OPTS --detail-out $ROOT/$O/detail_$tag.json > $ROOT/$O/kw_$tag.json 2> $ROOT/$O/kw_$tag.err )
     python profiles/summarize_rocprof.py $O/trace_$tag "kw_" > $O/rocprof_keyword_$tag.txt 2>&1; head -8 $O/rocprof_keyword_$tag.txt | cut -c1-190
     python - $O/detail_$tag.json $tag <<'PY'
 import json, sys

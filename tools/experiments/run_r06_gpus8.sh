@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 N=${1:-2000000}; W=${2:-8}
 O=gpurun_out/r06_gpus$W; mkdir -p $O
 ( time TSGPU_DIST_BACKEND=gloo MASTER_ADDR=127.0.0.1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port 29631 \
-    bench.py --gpus $W --steps 3 --warmup 1 --n-docs $N --batch 2000 --vec-batch 64 --no-cpu-baseline --detail-out $O/detail.json ) > $O/bench_gpus$W.json 2> $O/bench_gpus$W.err
+    bench.py --full --gpus $W --steps 3 --warmup 1 --n-docs $N --batch 2000 --vec-batch 64 --no-cpu-baseline --detail-out $O/detail.json ) > $O/bench_gpus$W.json 2> $O/bench_gpus$W.err
 echo "rc=$?"; tail -3 $O/bench_gpus$W.err | cut -c1-300
 python - $O/bench_gpus$W.json <<'PY'
 import json, sys

@@ -12,8 +12,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$ROOT/gpurun_out/prof_$TAG; P=$ROOT/gpurun_out/profiles_$R
 mkdir -p $O $P
 cd /tmp
-KW="python $ROOT/bench.py --workload keyword --no-cpu-baseline --no-extras --steps 3 --warmup 1"
-VEC="python $ROOT/bench.py --workload vector --no-cpu-baseline --no-extras --steps 3 --warmup 1"
+KW="python $ROOT/bench.py --full --workload keyword --no-cpu-baseline --no-extras --steps 3 --warmup 1"
+VEC="python $ROOT/bench.py --full --workload vector --no-cpu-baseline --no-extras --steps 3 --warmup 1"
 KWG="python $ROOT/bench.py --workload kwgeneral --no-cpu-baseline --steps 3 --warmup 1"     # two query_by fields + 10 candidate combinations per query (general kernels)
 if [ "${SKIP_PROF:-0}" != "1" ]; then          # SKIP_PROF=1: only the GPU tier, the smoke test and the bench line (the committed rocprof / PMC summaries stay)
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_kw -- $KW > $O/trace_kw.log 2>&1
@@ -52,7 +52,7 @@ mkdir -p profiles/$R && { ls $P/pmc_*.txt > /dev/null 2>&1 && cp $P/pmc_*.txt $P
 timeout 1500 python -m pytest tests -m gpu -x -q > $P/pytest_gpu_$TAG.txt 2>&1; tail -2 $P/pytest_gpu_$TAG.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $P/smoke_$TAG.txt 2>&1; tail -1 $P/smoke_$TAG.txt
 # (round 5: stdout = the compact line the driver parses; the full record = --detail-out; stderr carries a copy of it)
-( time timeout 1200 python bench.py --steps 20 --warmup 5 --detail-out $P/bench_all_${TAG}_detail.json ) > $P/bench_all_$TAG.json 2> $O/bench_all.err; grep -v BENCH_DETAIL $O/bench_all.err | tail -4; wc -c $P/bench_all_$TAG.json $P/bench_all_${TAG}_detail.json
+( time timeout 1200 python bench.py --full --steps 20 --warmup 5 --detail-out $P/bench_all_${TAG}_detail.json ) > $P/bench_all_$TAG.json 2> $O/bench_all.err; grep -v BENCH_DETAIL $O/bench_all.err | tail -4; wc -c $P/bench_all_$TAG.json $P/bench_all_${TAG}_detail.json
 # round 6: the HNSW leg at BASELINE config 3's size (10M x 768; the graph built on the device by tsgpu_vec_hnsw_build) + the kernel trace of a 2M-row bulk build
 if [ "${SKIP_HNSW10M:-0}" != "1" ]; then
 ( time timeout 1500 python bench.py --workload hnsw --no-cpu-baseline --hnsw-rows 10000000 ) > $P/bench_hnsw_10m.json 2> $O/bench_hnsw_10m.err; tail -3 $O/bench_hnsw_10m.err
