@@ -84,8 +84,24 @@ enum tsgpu_sort_kind {
     TSGPU_SORT_TEXT_MATCH = 0,      /* text_match_sentinel_value */
     TSGPU_SORT_SEQ_ID = 1,          /* seq_id_sentinel_value */
     TSGPU_SORT_INT64_COLUMN = 2,    /* sort_index[field]->find(seq_id), missing -> INT64_MIN */
-    TSGPU_SORT_VECTOR_DISTANCE = 3  /* vector_distance_sentinel_value -> float_to_int64_t(d) */
+    TSGPU_SORT_VECTOR_DISTANCE = 3, /* vector_distance_sentinel_value -> float_to_int64_t(d) */
+    /* The integer branches of Index::compute_sort_scores beyond a plain column (src/index.cpp:5733-5760, 5761-5834, 5892-5898). Served by the keyword,
+     * wildcard, candidates and grouped entry points of ONE context. tsgpu_vector_search_batch, tsgpu_hybrid_* (there the reference walks the hits in
+     * distance order with the forward-only cursor of :5817: not membership) and every tsgpu_group_* shard form answer 501 for a query that names one.
+     * Out of scope, 501 / left to the caller's CPU body: geo-distance sort (needs S2), the decay functions (libm's exp bit for bit), random_order,
+     * _vector_query(...) sort, reference / join sorts, _group_found; text-match and vector-distance bucketing happen after the Topster, on the host. */
+    TSGPU_SORT_EVAL = 4,            /* _eval(<filters>): `column` holds a sort-key HANDLE (tsgpu_sort_key_create_eval); the score is scores[e] of the FIRST
+                                       expression e whose id list holds the document, else 0 (:5809-5834). At most one _eval slot per query (501 beyond:
+                                       the reference shares one cursor vector between them, :5809-5811, its result depends on their order) */
+    TSGPU_SORT_INT64_COLUMN_MISSING_FIRST = 5, /* kind 2 with missing_values: first (:5892-5898): a value of INT64_MIN (missing — or really that value)
+                                       becomes INT64_MIN + 1 for ASC and INT64_MAX for DESC, before the ASC negation. missing_values: last and
+                                       missing_values: normal ARE kind 2 as it stands (INT64_MIN sorts last either way: -INT64_MIN == INT64_MIN) */
+    TSGPU_SORT_STRING_RANK = 6,     /* sort on a string field: `column` is an int64 column of adi_tree_t::rank(seq_id) values, INT64_MAX (adi_tree_t::NOT_FOUND)
+                                       for a document without a value (:5733-5735); then as kind 2 */
+    TSGPU_SORT_STRING_RANK_FLIP = 7 /* kind 6, but a value equal to INT64_MAX is negated first (:5750-5760, wrapping). The caller picks 7 exactly when
+                                       (order asc AND missing_values first) OR (order desc AND missing_values last) */
 };
+#define TSGPU_SORT_KEY_SLOTS 4096   /* sort-key handles that can be live at once per context (256 request threads x 3 slots, with room to spare) */
 
 /* vector_distance_type_t, include/field.h:92-95 */
 enum tsgpu_metric { TSGPU_METRIC_IP = 0, TSGPU_METRIC_COSINE = 1 };
@@ -201,6 +217,20 @@ int tsgpu_column_set(tsgpu_ctx* ctx, uint32_t column_id, const int64_t* values, 
 /* number of documents (num_seq_ids(), bounds the Topster capacity, src/index.cpp:3510) */
 int tsgpu_set_num_docs(tsgpu_ctx* ctx, uint32_t num_docs);
 
+/* The key a TSGPU_SORT_EVAL slot carries in tsgpu_sort_by::column. ids[e][0 .. n_ids[e]) = the documents expression e matches (eval.eval_ids_vec /
+ * eval_ids_count_vec: ascending, unique; an empty list is legal), scores[e] = eval.scores[e]; n_expr = 1..255; host arrays, uploaded ONCE, here — the
+ * reference evaluates the filters once per request and then runs many search_across_fields passes over the result, and a server may keep hot
+ * expressions alive across requests. In HBM the key has one of two forms with identical results: DENSE, a byte per document (first matching expression
+ * + 1; built by a scatter kernel, one byte load per candidate at query time), or SPARSE, the sorted lists probed by binary search. Option
+ * "sortkey_dense_div" (default 64, read at create): dense when (total ids) x div >= num_docs; 0 = always sparse, 1 = always dense.
+ * Returns 507 when all TSGPU_SORT_KEY_SLOTS handles are live; a query naming a handle that is not live gets 400.
+ * Threads: create and destroy may run concurrently with each other and with searches that do not name the handle, and stall no search (own stream,
+ * no lane and no index lock held). Destroying a handle an in-flight search names is a caller error (like freeing filter_ids mid-call). The device memory
+ * of a destroyed key is parked with the retired snapshots' buffers and freed by tsgpu_commit / tsgpu_destroy, never under a running batch.
+ * Counter "sort_keys_live". */
+int tsgpu_sort_key_create_eval(tsgpu_ctx* ctx, const uint32_t* const* ids, const uint32_t* n_ids, const int64_t* scores, uint32_t n_expr, uint16_t* handle_out);
+int tsgpu_sort_key_destroy(tsgpu_ctx* ctx, uint16_t handle);
+
 /* Publish all pending posting-list changes as ONE new immutable snapshot (RCU): searches that started before keep the snapshot they
  * run on, searches never wait for a commit, a failing commit leaves the previous snapshot in place. Incremental: re-written blocks
  * and the touched lists' descriptors are appended at the tails of the device arenas and a new descriptor table is swapped in;
@@ -223,7 +253,7 @@ int tsgpu_term_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, uin
 typedef struct tsgpu_sort_by {
     uint8_t kind;      /* tsgpu_sort_kind */
     int8_t order;      /* 1 = DESC, -1 = ASC (sort_order[], src/index.cpp:5901-5903) */
-    uint16_t column;   /* for TSGPU_SORT_INT64_COLUMN */
+    uint16_t column;   /* column id (kinds 2, 5, 6, 7) or sort-key handle (TSGPU_SORT_EVAL) */
 } tsgpu_sort_by;
 
 typedef struct tsgpu_kw_query {

@@ -108,6 +108,19 @@ static const int KW_FIND_PIPE_WORDS = TSGPU_KW_FIND_PIPE_WORDS;
 static const int KW_FIND_TILE_WORDS = TSGPU_KW_FIND_TILE_WORDS;
 static const int KW_TILE_WORDS = TSGPU_KW_TILE_WORDS;   // LDS tile of PACKED second-list ids per round (8 KB ~ 20 blocks of 12-bit ids); multiple of 256
 
+// One `_eval(...)` sort key (tsgpu_sort_key_create_eval; compute_sort_scores, src/index.cpp:5761-5834): the id lists of its expressions in one of two forms.
+// DENSE: dense[seq_id] = first matching expression + 1, 0 = none (one byte load per candidate). SPARSE (dense == nullptr): the sorted lists back to back in
+// ids[], expression e = ids[expr_off[e] .. expr_off[e + 1]), probed by binary search, expression by expression. scores[e] either way.
+struct SortKeyDesc {
+    const uint8_t* dense;
+    const uint32_t* ids;
+    const uint32_t* expr_off;        // [n_expr + 1]
+    const int64_t* scores;           // [n_expr]
+    uint32_t dense_len;              // bytes of dense[] (seq_ids beyond it match nothing)
+    uint32_t n_expr;
+};
+static const uint32_t KW_SORT_KEY_SLOTS = 4096;     // handles of the context's key table (IndexView::sort_keys)
+
 struct IndexView {
     const ListDesc* lists;
     const uint32_t* blk_last;
@@ -131,6 +144,7 @@ struct IndexView {
     const long long* t0;
     uint32_t ticks_per_us;
     uint32_t* cutoff;
+    const SortKeyDesc* sort_keys;    // the context's key table, KW_SORT_KEY_SLOTS entries (KwQueryDev::sort_col of a TSGPU_SORT_EVAL slot indexes it; the planner checked the handle)
 };
 
 // The kernel's IndexView argument RE-READ from the kernarg segment (s_load where it is used) instead of kept live: the find kernels use most of its
@@ -991,6 +1005,44 @@ __device__ inline int64_t float_to_int64_dev(float f) {       // Index::float_to
     if (i < 0) i ^= INT32_MAX;
     return (int64_t)i;
 }
+// The `_eval` branch (:5761-5834) for a document taken on its own: the score of the FIRST expression whose id list holds it, else 0. (The reference keeps one
+// forward-only cursor per expression; over ascending seq_ids — every caller of the keyword paths — that is plain membership.)
+__device__ inline int64_t sort_key_eval(const SortKeyDesc& d, uint32_t seq_id) {
+    if (d.dense) {
+        const uint32_t e = seq_id < d.dense_len ? d.dense[seq_id] : 0u;
+        return e ? d.scores[e - 1] : 0;
+    }
+    for (uint32_t e = 0; e < d.n_expr; e++) {
+        uint32_t lo = d.expr_off[e];
+        const uint32_t end = d.expr_off[e + 1];
+        uint32_t hi = end;
+        while (lo < hi) {                                   // std::lower_bound (:5823)
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (d.ids[mid] < seq_id) lo = mid + 1; else hi = mid;
+        }
+        if (lo < end && d.ids[lo] == seq_id) return d.scores[e];
+    }
+    return 0;
+}
+// Builds the DENSE form of a key: dense[id] = tag (= expression + 1) for the ids of ONE expression. The host launches it once per expression, LAST to FIRST on one
+// stream, so where lists overlap the first expression's byte is the one that stays; ids are unique within a launch: plain byte stores, no atomics.
+__global__ __launch_bounds__(256) void sort_key_scatter_kernel(const uint32_t* __restrict__ ids, uint32_t n, uint8_t* __restrict__ dense, uint32_t dense_len, uint32_t tag) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t id = ids[i];
+        if (id < dense_len) dense[id] = (uint8_t)tag;
+    }
+}
+// the sort kinds beyond the four of the headline path (include/tsgpu.h): _eval, missing_values: first on a numeric column, string ranks
+__device__ inline int64_t sort_key_value(const IndexView& ix, uint32_t kind, uint32_t col, int order, uint32_t seq_id) {
+    if (kind == 4) return sort_key_eval(ix.sort_keys[col < KW_SORT_KEY_SLOTS ? col : 0], seq_id);
+    int64_t v = (col < ix.n_columns && seq_id < ix.column_len[col]) ? ix.columns[col][seq_id] : (kind == 5 ? INT64_MIN : INT64_MAX);
+    if (kind == 5) { if (v == INT64_MIN) v = order == -1 ? INT64_MIN + 1 : INT64_MAX; }                 // (:5892-5898)
+    else if (kind == 7 && v == INT64_MAX) v = (int64_t)(0ull - (uint64_t)v);                            // adi_tree_t::NOT_FOUND, flipped (:5750-5760)
+    return v;
+}
+// KEYS = false: no query of the launch has a slot of kind >= TSGPU_SORT_EVAL (the planner knows) — the score kernel's PLAIN instantiations, i.e. the headline
+// path, are compiled without those branches (profiles/r07/sortkeys_resource_usage.txt: with them the <3, 512, false, false, true> score kernel spilled 7 more VGPRs).
+template <bool KEYS = true>
 __device__ inline ScoredHit sort_scores(const IndexView& ix, const KwQueryDev& q, uint32_t seq_id, uint64_t agg, uint32_t off_words,
                                         bool override_text_match = true, float vector_distance = 0.0f) {
     int64_t sc[3] = {0, 0, 0};
@@ -1004,7 +1056,9 @@ __device__ inline ScoredHit sort_scores(const IndexView& ix, const KwQueryDev& q
             else if (q.sort_kind[i] == 2) {
                 const uint32_t c = q.sort_col[i];
                 v = (c < ix.n_columns && seq_id < ix.column_len[c]) ? ix.columns[c][seq_id] : INT64_MIN;
-            } else v = float_to_int64_dev(vector_distance);   // (:5835-5836; keyword passes hand 0: float_to_int64_t(0) == 0)
+            } else if (q.sort_kind[i] == 3) v = float_to_int64_dev(vector_distance);   // (:5835-5836; keyword passes hand 0: float_to_int64_t(0) == 0)
+            else if constexpr (KEYS) v = sort_key_value(ix, q.sort_kind[i], q.sort_col[i], q.sort_order[i], seq_id);
+            else v = 0;
             if (q.sort_order[i] == -1) v = (int64_t)(0ull - (uint64_t)v);
             sc[i] = v;
         }
@@ -1023,7 +1077,7 @@ __device__ inline ScoredHit sort_scores(const IndexView& ix, const KwQueryDev& q
 
 // score_results2 + compute_aggregated_score + compute_sort_scores for ONE query_by field (plain string); pos[t] = posting
 // position of found token t
-template <int TMAX>
+template <int TMAX, bool KEYS = true>
 __device__ inline ScoredHit score_hit(const IndexView& ix, const KwQueryDev& q, uint32_t seq_id, const uint32_t (&pos)[TMAX]) {
     const uint32_t T = q.n_lists;
     uint32_t off_words = 0;
@@ -1038,7 +1092,7 @@ __device__ inline ScoredHit score_hit(const IndexView& ix, const KwQueryDev& q, 
     }
     AggState st;
     agg_add(st, q.match_type, field_match_score<TMAX>(q, runs, T), q.weight);      // (string[] fields take the multi-field kernel: the planner routes them)
-    return sort_scores(ix, q, seq_id, agg_finish(st, q, T), off_words);
+    return sort_scores<KEYS>(ix, q, seq_id, agg_finish(st, q, T), off_words);
 }
 
 // the same for several query_by fields: pos[t * KW_MAX_FIELDS + f] = position of found token t in field f's list, or KW_NONE.
@@ -1123,7 +1177,7 @@ __device__ inline uint64_t agg_score_mf(const IndexView& ix, const KwQueryDev& q
     }
     return agg_finish(st, q, tokens_found);
 }
-template <int TMAX, bool ARR = true>
+template <int TMAX, bool ARR = true, bool KEYS = true>
 __device__ inline ScoredHit score_hit_mf(const IndexView& ix, const KwQueryDev& q, const KwQueryMF& mf, uint32_t seq_id,
                                          const uint32_t (&pos)[TMAX * KW_MAX_FIELDS]) {
     uint32_t off_words = 0;
@@ -1137,7 +1191,7 @@ __device__ inline ScoredHit score_hit_mf(const IndexView& ix, const KwQueryDev& 
         if ((uint32_t)t >= q.n_required && (uint32_t)t < q.n_lists && any) tokens_found++;
     }
     const uint64_t agg = agg_score_mf<TMAX, ARR>(ix, q, mf, pos, tokens_found, off_words);
-    return sort_scores(ix, q, seq_id, agg, off_words);
+    return sort_scores<KEYS>(ix, q, seq_id, agg, off_words);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1239,7 +1293,7 @@ struct KwSmem {
     uint32_t f_first, f_frank, f_rp, f_ep, f_c0, f_c1, f_cnt0, f_cnt1;
 };
 
-// PLAIN (score kernel only): no query of the launch has filter ids or excluded ids and no caller keeps the matched ids — the host knows, and the
+// PLAIN (score kernel only): no query of the launch has filter ids, excluded ids or a sort slot of kind >= TSGPU_SORT_EVAL and no caller keeps the matched ids — the host knows, and the
 // instantiation without those paths is a smaller kernel (registers, not LDS, set the score kernel's occupancy).
 template <int TMAX, int CAP, bool MF, bool S2, bool SCORE, bool PLAIN = false>
 __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& sm, const IndexView& ix, const KwQueryDev& q, uint32_t n_take,
@@ -1276,12 +1330,12 @@ __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& s
             uint32_t pos[NP];
 #pragma unroll
             for (int k = 0; k < NP; k++) pos[k] = sm.qf_pos[k][t];
-            if constexpr (MF) h = score_hit_mf<TMAX, !PLAIN>(ix, q, ix.mf[q.mf_index], seq_id, pos);     // (PLAIN multi-field launches: no string[] field either)
+            if constexpr (MF) h = score_hit_mf<TMAX, !PLAIN, !PLAIN>(ix, q, ix.mf[q.mf_index], seq_id, pos);     // (PLAIN multi-field launches: no string[] field and no sort-key slot either)
             else {
 #if defined(TSGPU_EXP) && TSGPU_EXP == 6
                 h.s0 = (int64_t)(seq_id * 2654435761u); h.s1 = (int64_t)pos[0] + pos[TMAX - 1]; h.s2 = 0; h.text_match = h.s0; h.off_words = 1;
 #else
-                h = score_hit<TMAX>(ix, q, seq_id, pos);
+                h = score_hit<TMAX, !PLAIN>(ix, q, seq_id, pos);
 #endif
             }
         }

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void kw_plan_resolve_kernel(KwPlanParams pp, c
     uint32_t n_num = 0;
     for (uint32_t s = 0; s < 3; s++) if (s < r.n_sort) {
         q.sort_kind[s] = r.sort_kind[s]; q.sort_order[s] = r.sort_order[s]; q.sort_col[s] = r.sort_col[s];
-        if (r.sort_kind[s] == TSGPU_SORT_INT64_COLUMN) n_num++;
+        if (r.sort_kind[s] == TSGPU_SORT_INT64_COLUMN || r.sort_kind[s] >= TSGPU_SORT_EVAL) n_num++;      // (a column, a key or a rank read per hit; the host pre-scan checked the handle / column)
     }
     // tokens -> lists (a token the field does not hold is skipped, src/index.cpp:5651-5655)
     const uint32_t f_off = r.field < 64 ? pp.dense[2 * r.field] : 0, f_n = r.field < 64 ? pp.dense[2 * r.field + 1] : 0;

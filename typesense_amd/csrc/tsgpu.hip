@@ -60,6 +60,7 @@ IndexView make_view(tsgpu_ctx* ctx, const Snapshot& sn) {
     v.mf = nullptr;                                   // per lane: set by the batch
     v.fbits = nullptr;
     v.t0 = nullptr; v.ticks_per_us = 100; v.cutoff = nullptr;
+    v.sort_keys = ctx->d_sort_keys.as<SortKeyDesc>();
     return v;
 }
 
@@ -157,6 +158,13 @@ int tsgpu_create(int device_ordinal, tsgpu_ctx** out) {
         good = good && hipEventCreateWithFlags(&L.ev_block, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
         good = good && hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming) == hipSuccess;
     }
+    // the sort-key table (tsgpu_sort_key_create_eval): every slot exists from the start, so the pointer the kernels hold never moves
+    static_assert(TSGPU_SORT_KEY_SLOTS == KW_SORT_KEY_SLOTS && TSGPU_SORT_KEY_SLOTS <= 65536, "a handle is the uint16_t a sort slot carries");
+    good = good && hipStreamCreateWithFlags(&ctx->sk_stream, hipStreamNonBlocking) == hipSuccess;
+    good = good && ctx->d_sort_keys.reserve((size_t)TSGPU_SORT_KEY_SLOTS * sizeof(SortKeyDesc)) == TSGPU_OK;
+    good = good && hipMemset(ctx->d_sort_keys.p, 0, (size_t)TSGPU_SORT_KEY_SLOTS * sizeof(SortKeyDesc)) == hipSuccess;
+    ctx->sort_keys.resize(TSGPU_SORT_KEY_SLOTS);
+    for (uint32_t h = TSGPU_SORT_KEY_SLOTS; h-- > 0;) ctx->sk_free.push_back((uint16_t)h);      // (handed out from 0 upwards)
     if (!good) { tsgpu_destroy(ctx); return fail(TSGPU_ERR_DEVICE, "tsgpu_create: stream / event creation failed"); }
     *out = ctx;
     return ok();
@@ -179,6 +187,9 @@ void tsgpu_destroy(tsgpu_ctx* ctx) {
     deferred_frees().drain();
     ctx->d_col_ptrs.release(); ctx->d_col_len.release(); ctx->d_prof.release();
     for (auto& c : ctx->columns) c.data.release();
+    for (auto& k : ctx->sort_keys) k.buf.release();
+    ctx->d_sort_keys.release();
+    if (ctx->sk_stream) (void)hipStreamDestroy(ctx->sk_stream);
     for (auto& ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->aux_ev) if (ev) (void)hipEventDestroy(ev);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -242,6 +253,104 @@ int tsgpu_set_num_docs(tsgpu_ctx* ctx, uint32_t num_docs) {
     return ok();
 }
 
+// ---------------------------------------------------------------- `_eval` sort keys (TSGPU_SORT_EVAL)
+int tsgpu_sort_key_create_eval(tsgpu_ctx* ctx, const uint32_t* const* ids, const uint32_t* n_ids, const int64_t* scores, uint32_t n_expr, uint16_t* handle_out) {
+    if (!ctx || !handle_out || !scores || !n_ids || !ids) return fail(TSGPU_ERR_INVALID, "tsgpu_sort_key_create_eval: NULL argument");
+    if (n_expr < 1 || n_expr > 255) return fail(TSGPU_ERR_INVALID, "tsgpu_sort_key_create_eval: n_expr must be 1..255 (the dense form keeps expression + 1 in a byte)");
+    uint64_t total = 0;
+    uint32_t max_id_p1 = 0;
+    for (uint32_t e = 0; e < n_expr; e++) {
+        if (n_ids[e] && !ids[e]) return fail(TSGPU_ERR_INVALID, "tsgpu_sort_key_create_eval: an id list is NULL");
+        total += n_ids[e];
+        if (n_ids[e]) {
+            if (ids[e][n_ids[e] - 1] == 0xFFFFFFFFu) return fail(TSGPU_ERR_INVALID, "tsgpu_sort_key_create_eval: id out of range");
+            max_id_p1 = std::max(max_id_p1, ids[e][n_ids[e] - 1] + 1);          // (ascending: the last id is the largest)
+        }
+    }
+    if (total > 0xFFFFFFFFull) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_sort_key_create_eval: more than 2^32 - 1 ids");
+    uint16_t handle;
+    long long div;
+    uint32_t num_docs;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        if (ctx->sk_free.empty()) return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_sort_key_create_eval: every sort-key handle is live (TSGPU_SORT_KEY_SLOTS)");
+        handle = ctx->sk_free.back(); ctx->sk_free.pop_back();                    // (reserved: not live until the upload is done)
+        div = ctx->sortkey_dense_div;
+        num_docs = ctx->num_docs;
+    }
+    (void)hipSetDevice(ctx->device);
+    const uint32_t dense_len = std::max(num_docs, max_id_p1);
+    const bool dense = dense_len != 0 && (div == 1 || (div > 1 && total * (uint64_t)div >= (uint64_t)num_docs));
+    // one allocation: [scores: 8 x n_expr | expr_off: 4 x (n_expr + 1) | ids: 4 x total | dense: dense_len bytes]
+    const size_t at_off = (size_t)8 * n_expr, at_ids = (at_off + (size_t)4 * (n_expr + 1) + 15) & ~(size_t)15, at_dense = (at_ids + (size_t)4 * total + 15) & ~(size_t)15;
+    const size_t bytes = at_dense + (dense ? dense_len : 0) + 16;
+    DevBuf buf;
+    auto give_back = [&](int rc) {
+        if (buf.p) ctx->retire_bin->put(buf);
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        ctx->sk_free.push_back(handle);
+        return rc;
+    };
+    if (hipMalloc(&buf.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.p = nullptr;
+        return give_back(fail(TSGPU_ERR_NO_MEMORY, "tsgpu_sort_key_create_eval: device allocation failed"));
+    }
+    buf.cap = bytes;
+    uint8_t* const base = (uint8_t*)buf.p;
+    std::vector<uint32_t> expr_off(n_expr + 1, 0u);
+    for (uint32_t e = 0; e < n_expr; e++) expr_off[e + 1] = expr_off[e] + n_ids[e];
+    hipStream_t s = ctx->sk_stream;
+    bool good = hipMemcpyAsync(base, scores, (size_t)8 * n_expr, hipMemcpyHostToDevice, s) == hipSuccess;
+    good = good && hipMemcpyAsync(base + at_off, expr_off.data(), (size_t)4 * (n_expr + 1), hipMemcpyHostToDevice, s) == hipSuccess;
+    for (uint32_t e = 0; e < n_expr && good; e++)
+        if (n_ids[e]) good = hipMemcpyAsync(base + at_ids + (size_t)4 * expr_off[e], ids[e], (size_t)4 * n_ids[e], hipMemcpyHostToDevice, s) == hipSuccess;
+    if (dense && good) {
+        good = hipMemsetAsync(base + at_dense, 0, dense_len, s) == hipSuccess;
+        // LAST expression first, on one stream: where lists overlap the FIRST expression's byte is the one written last (ids are unique within a launch)
+        for (uint32_t e = n_expr; e-- > 0 && good;) {
+            if (!n_ids[e]) continue;
+            const uint32_t blocks = std::min<uint32_t>((n_ids[e] + 255) / 256, 4096u);
+            hipLaunchKernelGGL(sort_key_scatter_kernel, dim3(blocks), dim3(256), 0, s, (const uint32_t*)(base + at_ids) + expr_off[e], n_ids[e], base + at_dense, dense_len, (uint32_t)(e + 1));
+        }
+        good = good && hipGetLastError() == hipSuccess;
+    }
+    SortKeyDesc d;
+    d.dense = dense ? base + at_dense : nullptr;
+    d.ids = (const uint32_t*)(base + at_ids);
+    d.expr_off = (const uint32_t*)(base + at_off);
+    d.scores = (const int64_t*)base;
+    d.dense_len = dense ? dense_len : 0u;
+    d.n_expr = n_expr;
+    good = good && hipMemcpyAsync(ctx->d_sort_keys.as<SortKeyDesc>() + handle, &d, sizeof d, hipMemcpyHostToDevice, s) == hipSuccess;
+    good = good && hipStreamSynchronize(s) == hipSuccess;             // (this stream only: the key is complete before any query can name its handle)
+    if (!good) { (void)hipGetLastError(); return give_back(fail(TSGPU_ERR_DEVICE, "tsgpu_sort_key_create_eval: upload failed")); }
+    {
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        SortKeyHost& k = ctx->sort_keys[handle];
+        k.live = true; k.dense = dense; k.buf = buf; k.n_ids = total; k.n_expr = n_expr;
+    }
+    ctx->sort_keys_live.fetch_add(1);
+    *handle_out = handle;
+    return ok();
+}
+
+int tsgpu_sort_key_destroy(tsgpu_ctx* ctx, uint16_t handle) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    DevBuf buf;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        if (handle >= ctx->sort_keys.size() || !ctx->sort_keys[handle].live) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_sort_key_destroy: no such sort key");
+        SortKeyHost& k = ctx->sort_keys[handle];
+        buf = k.buf;
+        k = SortKeyHost();
+        ctx->sk_free.push_back(handle);
+    }
+    ctx->sort_keys_live.fetch_sub(1);
+    ctx->retire_bin->put(buf);            // no hipFree here: a batch planned before this call may still read the key (freed by tsgpu_commit / tsgpu_destroy)
+    return ok();
+}
+
 int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return fail(TSGPU_ERR_INVALID, "tsgpu_set_option: NULL argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -254,6 +363,11 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "kw_cost_fixed")) { ctx->kw_cost_fixed = (uint32_t)std::max<int64_t>(value, 0); return ok(); }
     if (!strcmp(name, "kw_sort_work")) { ctx->kw_sort_work = value != 0; return ok(); }
     if (!strcmp(name, "kw_two_kernels")) { ctx->kw_two_kernels = value != 0; return ok(); }
+    if (!strcmp(name, "sortkey_dense_div")) {
+        if (value < 0 || value > (1ll << 31)) return fail(TSGPU_ERR_INVALID, "sortkey_dense_div out of range (0..2^31)");
+        std::lock_guard<std::mutex> sk(ctx->sk_mu);
+        ctx->sortkey_dense_div = value; return ok();
+    }
     if (!strcmp(name, "kw_device_plan_min_queries")) { ctx->kw_device_plan_min_queries = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 30); return ok(); }
     if (!strcmp(name, "kw_pair_blocks")) { ctx->kw_pair_blocks = value != 0; return ok(); }
     if (!strcmp(name, "doc_range_lo")) { ctx->doc_range_set = true; ctx->doc_range_lo = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 0xFFFFFFFFll); return ok(); }
@@ -375,6 +489,7 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "kw_book_us")) { *out = ctx->kw_book_us.load(); return ok(); }
     if (!strcmp(name, "kw_device_plans")) { *out = ctx->kw_device_plans.load(); return ok(); }                     // batches planned on the device / sent back to the host planner
     if (!strcmp(name, "kw_device_plan_fallbacks")) { *out = ctx->kw_device_plan_fallbacks.load(); return ok(); }
+    if (!strcmp(name, "sort_keys_live")) { *out = ctx->sort_keys_live.load(); return ok(); }                         // tsgpu_sort_key_create_eval minus _destroy
     if (!strcmp(name, "kw_iddir_built")) { *out = ctx->kw_iddir_built; return ok(); }                               // id directories (re)built by commits so far
     if (!strcmp(name, "kw_iddir_lists")) { const auto sn = ctx->snapshot(); uint64_t n = 0; if (sn) for (const auto& r : sn->dir_of) n += r ? 1 : 0; *out = n; return ok(); }   // lists of the current snapshot that carry one
     if (!strcmp(name, "batch_exec_us")) { *out = ctx->batch_exec_us.load(); return ok(); }           // coalesced rounds: batch execution / hand-out to the callers
@@ -406,7 +521,7 @@ struct Plan {
     uint64_t fbits_words = 0;                             // rank bitmaps of the filtered multi-field queries
     bool any_deadline = false;                            // some query carries a deadline: stamp the batch start, collect cutoff flags
     bool any_s2 = false;              // some query has a third sort key
-    bool any_aux = false;             // some query has filter ids or excluded ids (else the score kernel's PLAIN instantiation serves the batch)
+    bool any_aux = false;             // some query has filter ids, excluded ids or a sort slot of kind >= TSGPU_SORT_EVAL (else the score kernel's PLAIN instantiation serves the batch)
     bool any_array = false;           // some multi-field query has a string[] field
     uint32_t mf_max_fields = 0;       // most query_by fields of any multi-field query (<= 2: the pipelined find kernel, kw_find_mf2.hip.h)
     std::vector<uint32_t> aux;
@@ -529,13 +644,8 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             if (in.n_sort > TSGPU_MAX_SORT_KEYS) { P.status[i] = TSGPU_ERR_INVALID; continue; }
             if (in.n_filter != 0 && !in.filter_ids) { P.status[i] = TSGPU_ERR_INVALID; continue; }
             if (in.match_type > TSGPU_SUM_SCORE) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-            bool bad_sort = false;
-            for (uint32_t s = 0; s < in.n_sort; s++) {
-                if (in.sort[s].kind > TSGPU_SORT_INT64_COLUMN && !(vflat && in.sort[s].kind == TSGPU_SORT_VECTOR_DISTANCE)) bad_sort = true;   // vector_distance belongs to the vector/hybrid entry points
-                if (in.sort[s].kind == TSGPU_SORT_INT64_COLUMN && in.sort[s].column >= ctx->columns.size()) bad_sort = true;
-                if (in.sort[s].order != 1 && in.sort[s].order != -1) bad_sort = true;
-            }
-            if (bad_sort) { unsupported("sort"); continue; }
+            uint64_t sort_bytes_per_id = 0;                             // what the sort slots read per ranked document (list_bytes)
+            if (const int sort_rc = check_sort_slots(ctx, in.sort, in.n_sort, vflat != nullptr, vflat != nullptr, &sort_bytes_per_id)) { P.status[i] = sort_rc; continue; }   // vector_distance belongs to the vector/hybrid entry points
             const uint32_t k = vflat ? std::max<uint32_t>(in.topster_size, 1) : resolve_topster_size(ctx, in);     // (the vector branch resolved it against ITS filter / row count)
             if (k > TSGPU_MAX_TOPK) { unsupported("topster_size"); continue; }
             if (in.deadline_us != 0 && now > in.deadline_us) { P.status[i] = TSGPU_ERR_DEADLINE; P.cutoff[i] = 1; continue; }
@@ -547,7 +657,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
                 q.n_sort = (uint8_t)in.n_sort;
                 for (uint32_t s = 0; s < in.n_sort; s++) {
                     q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
-                    if (in.sort[s].kind == TSGPU_SORT_INT64_COLUMN) A.n_numeric_sort_q++;
+                    if (sort_kind_reads_key(in.sort[s].kind)) A.n_numeric_sort_q++;
                 }
                 q.k = k;
                 A.max_k = std::max(A.max_k, k);
@@ -584,9 +694,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
                 }
                 q.wild_n_ids = n_ids;
                 if (n_ids == 0) continue;                                               // (nothing of this query on this shard: zero hits, status 0)
-                uint32_t n_num = 0;
-                for (uint32_t s = 0; s < in.n_sort; s++) n_num += in.sort[s].kind == TSGPU_SORT_INT64_COLUMN;
-                A.list_bytes += 4ull * in.n_filter + 8ull * n_ids * n_num;      // the id array + one column value per id and numeric key
+                A.list_bytes += 4ull * in.n_filter + sort_bytes_per_id * n_ids;      // the id array + one column value (a key byte, the key's lists) per id and key slot
                 q.ids_out_off = A.ids_total;
                 const uint32_t n_blocks = (n_ids + BLOCK_IDS - 1) / BLOCK_IDS;
                 if (keep_ids) A.ids_total += (uint64_t)n_blocks * BLOCK_IDS;
@@ -657,7 +765,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             if (in.n_sort > 2) A.any_s2 = true;
             for (uint32_t s = 0; s < in.n_sort; s++) {
                 q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
-                if (in.sort[s].kind == TSGPU_SORT_INT64_COLUMN) A.n_numeric_sort_q++;
+                if (sort_kind_reads_key(in.sort[s].kind)) A.n_numeric_sort_q++;
             }
             q.k = k;
             A.max_k = std::max(A.max_k, k);
@@ -665,6 +773,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             q.n_excl = in.n_excluded;
             q.n_filt = in.n_filter;
             if (in.n_excluded || in.n_filter) A.any_aux = true;
+            for (uint32_t s = 0; s < in.n_sort; s++) if (in.sort[s].kind >= TSGPU_SORT_EVAL) A.any_aux = true;      // (the PLAIN score kernels carry no sort-key code)
             if (in.n_excluded) {
                 if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; continue; }
                 A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
@@ -866,7 +975,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     if ((rc = L.h_plan.reserve((size_t)n_queries * sizeof(KwPlanIn) + 64))) return rc;
     KwPlanIn* hin = (KwPlanIn*)L.h_plan.p;
     const uint32_t n_columns = (uint32_t)ctx->columns.size();
-    std::atomic<int> bad{0};
+    std::atomic<int> bad{0}, any_keys{0};
     auto scan = [&](uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; i++) {
             const tsgpu_kw_query& in = queries[i];
@@ -874,7 +983,9 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
                       in.deadline_us == 0 && in.n_sort <= TSGPU_MAX_SORT_KEYS && in.match_type <= TSGPU_SUM_SCORE && in.field_ids[0] < 64;
             if (ok) { auto it = snap.field_is_array.find(in.field_ids[0]); ok = it != snap.field_is_array.end() && !it->second; }
             for (uint32_t k = 0; ok && k < in.n_sort; k++)
-                ok = in.sort[k].kind <= TSGPU_SORT_INT64_COLUMN && (in.sort[k].kind != TSGPU_SORT_INT64_COLUMN || in.sort[k].column < n_columns) && (in.sort[k].order == 1 || in.sort[k].order == -1);
+                ok = in.sort[k].kind != TSGPU_SORT_VECTOR_DISTANCE && (!sort_kind_reads_column(in.sort[k].kind) || in.sort[k].column < n_columns);
+            for (uint32_t k = 0; ok && k < in.n_sort; k++) if (in.sort[k].kind >= TSGPU_SORT_EVAL) any_keys.store(1, std::memory_order_relaxed);
+            ok = ok && check_sort_slots(ctx, in.sort, in.n_sort, false, false, nullptr) == TSGPU_OK;      // (a bad handle, two _eval slots, ...: the host planner reports them per query)
             const uint32_t k = ok ? resolve_topster_size(ctx, in) : 0;
             if (!ok || k > TSGPU_MAX_TOPK) { bad.store(1); return; }
             KwPlanIn& r = hin[i];
@@ -946,6 +1057,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     P.status.assign(n_queries, TSGPU_OK);
     P.cutoff.assign(n_queries, 0);
     P.max_k = std::max<uint32_t>(t1.max_k, 1); P.any_s2 = t1.any_s2 != 0; P.list_bytes = t1.list_bytes; P.n_numeric_sort_q = t1.n_numeric_sort_q;
+    P.any_aux = any_keys.load() != 0;                  // (a sort-key slot in the batch: the score kernels with the sort-key code)
     DP.on = true;
     DP.dq = dq; DP.dw = dw; DP.daux = (const uint32_t*)(dp + at_aux); DP.hoff = (const uint64_t*)hoff;
     DP.n_work[0] = t1.n_work[0]; DP.n_work[1] = t1.n_work[1]; DP.hit_blocks[0] = t1.hit_blocks[0]; DP.hit_blocks[1] = t1.hit_blocks[1];
@@ -1594,8 +1706,8 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
         if (!dev_out && out->num_matched) {
             for (uint32_t i = 0; i < n_queries; i++) {
                 uint32_t n_num = 0;
-                if (DP.on) { for (uint32_t k = 0; k < queries[i].n_sort; k++) if (queries[i].sort[k].kind == TSGPU_SORT_INT64_COLUMN) n_num++; }
-                else for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (P.q[i].sort_kind[k] == TSGPU_SORT_INT64_COLUMN) n_num++;
+                if (DP.on) { for (uint32_t k = 0; k < queries[i].n_sort; k++) if (sort_kind_reads_key(queries[i].sort[k].kind)) n_num++; }
+                else for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (sort_kind_reads_key(P.q[i].sort_kind[k])) n_num++;
                 bytes += 4ull * off_words[i] + 8ull * out->num_matched[i] * n_num;
             }
         } else {
@@ -1631,7 +1743,7 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
             }
             for (uint32_t i = 0; nm && !DP.on && i < n_queries; i++) {
                 uint32_t n_num = 0;
-                for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (P.q[i].sort_kind[k] == TSGPU_SORT_INT64_COLUMN) n_num++;
+                for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (sort_kind_reads_key(P.q[i].sort_kind[k])) n_num++;
                 sb += nm[i] * (4ull * ((P.q[i].n_lists <= 3 ? 3 : KW_MAX_TOKENS) + 1) + 56ull * P.q[i].n_lists + 8ull * n_num);
             }
             tt.score_requested_bytes = sb;

@@ -586,6 +586,7 @@ int tsgpu_group_create_local(tsgpu_ctx* const* members, uint32_t n_members, int 
         if (rc) return rccl_fail("ncclCommInitAll", rc);
         for (uint32_t i = 0; i < n_members; i++) g->m[i].comm = comms[i];
     }
+    for (auto& mem : g->m) mem.ctx->group_member.fetch_add(1);        // (a member refuses the sort kinds >= TSGPU_SORT_EVAL: a sort key is one context's)
     *out = g.release();
     return ok();
 }
@@ -607,6 +608,7 @@ int tsgpu_group_create_rank(tsgpu_ctx* ctx, const uint8_t id[128], uint32_t rank
     if (rc) return rccl_fail("ncclCommInitRank", rc);
     // the agreement step's buffers exist from here on: a reservation that fails inside agree() would leave the other ranks in its collective
     if ((rc = g->m[0].agree_d.reserve((size_t)(n_ranks + 1) * 8)) || (rc = g->m[0].agree_h.reserve((size_t)(n_ranks + 1) * 8))) { (void)r->CommDestroy(g->m[0].comm); return rc; }
+    for (auto& mem : g->m) mem.ctx->group_member.fetch_add(1);        // (a member refuses the sort kinds >= TSGPU_SORT_EVAL: a sort key is one context's)
     *out = g.release();
     return ok();
 }
@@ -622,6 +624,7 @@ int tsgpu_group_create_rank_host(tsgpu_ctx* ctx, const tsgpu_host_collectives* c
     g->coll = *coll;
     g->m.resize(1);
     g->m[0].ctx = ctx;
+    for (auto& mem : g->m) mem.ctx->group_member.fetch_add(1);        // (a member refuses the sort kinds >= TSGPU_SORT_EVAL: a sort key is one context's)
     *out = g.release();
     return ok();
 }
@@ -630,6 +633,7 @@ void tsgpu_group_destroy(tsgpu_group* g) {
     if (g) for (auto& mem : g->m) for (hipEvent_t& e : mem.ev) if (e) { (void)hipSetDevice(mem.ctx->device); (void)hipEventDestroy(e); e = nullptr; }
     if (!g) return;
     for (auto& mem : g->m) {
+        mem.ctx->group_member.fetch_sub(1);
         (void)hipSetDevice(mem.ctx->device);
         if (mem.comm && rccl()->CommDestroy) (void)rccl()->CommDestroy(mem.comm);
         DevBuf* cb[] = {&mem.c_pass, &mem.c_mask, &mem.c_found, &mem.c_meta, &mem.c_meta_all, &mem.c_qi, &mem.c_fp, &mem.c_fp_all, &mem.c_tok, &mem.c_tok_all};

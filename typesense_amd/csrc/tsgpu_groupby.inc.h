@@ -79,10 +79,8 @@ static int gb_translate(const tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_
     q.mf_index = KW_NONE;
     q.syn_orig_num_tokens = -1;
     if (in.n_sort > TSGPU_MAX_SORT_KEYS) return TSGPU_ERR_INVALID;
+    if (const int sort_rc = check_sort_slots(const_cast<tsgpu_ctx*>(ctx), in.sort, in.n_sort, false, false, nullptr)) return sort_rc;
     for (uint32_t s = 0; s < in.n_sort; s++) {
-        if (in.sort[s].kind > TSGPU_SORT_INT64_COLUMN) return TSGPU_ERR_UNSUPPORTED;
-        if (in.sort[s].kind == TSGPU_SORT_INT64_COLUMN && in.sort[s].column >= ctx->columns.size()) return TSGPU_ERR_UNSUPPORTED;
-        if (in.sort[s].order != 1 && in.sort[s].order != -1) return TSGPU_ERR_UNSUPPORTED;
         q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
     }
     q.n_sort = (uint8_t)in.n_sort;

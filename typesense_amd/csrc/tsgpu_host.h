@@ -303,6 +303,10 @@ struct Snapshot {            // immutable view of all posting lists; published b
     }
 };
 
+// One live `_eval` sort key (tsgpu_sort_key_create_eval): its device allocation — [scores | expr_off | ids | dense bytes], described to the kernels by the
+// SortKeyDesc at its handle's slot of ctx->d_sort_keys — and what the planner's byte accounting needs.
+struct SortKeyHost { bool live = false, dense = false; DevBuf buf; uint64_t n_ids = 0; uint32_t n_expr = 0; };
+
 struct ColumnDev { DevBuf data; uint32_t n = 0; std::vector<int64_t> host; /* mirror for the <=k-hit host steps (vector / hybrid) */ };
 
 struct VecField;             // tsgpu_vec.hip
@@ -496,6 +500,18 @@ struct tsgpu_ctx {
     uint64_t commit_last_us = 0, commit_last_uploaded_bytes = 0, commit_full_count = 0, commit_incremental_count = 0;
     std::vector<tsgpu::ColumnDev> columns;
     tsgpu::DevBuf d_col_ptrs, d_col_len;
+    // `_eval` sort keys (tsgpu_sort_key_create_eval / _destroy): a table of TSGPU_SORT_KEY_SLOTS handles. sk_mu guards the HOST table only and is held for
+    // a few loads — by create / destroy and by a planner that checks a query's handle — never across a device call: uploads and the scatter kernel run on
+    // sk_stream, outside every lane and outside ctx->mu, so neither call stalls a round. The device table (d_sort_keys) is allocated once, at tsgpu_create:
+    // a kernel reads only the slots its queries name, create overwrites only the slot it was handed.
+    std::mutex sk_mu;
+    std::vector<tsgpu::SortKeyHost> sort_keys;
+    std::vector<uint16_t> sk_free;
+    std::atomic<uint64_t> sort_keys_live{0};
+    tsgpu::DevBuf d_sort_keys;
+    hipStream_t sk_stream = nullptr;
+    std::atomic<int> group_member{0};                // tsgpu_groups this context serves; while > 0 the sort kinds >= TSGPU_SORT_EVAL are refused (501) in every entry point
+    long long sortkey_dense_div = 64;                // option "sortkey_dense_div": dense form when total ids x div >= num_docs (0 = always sparse, 1 = always dense); read at create
     uint32_t num_docs = 0;
     bool num_docs_set = false;
 
@@ -584,6 +600,46 @@ struct tsgpu_ctx {
     hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // created on first use, on the context's device
     bool scan_events_valid = false;                  // ev[6]/ev[7] bracket the main k-NN scan of the last batch's first query group
 };
+
+// ---- the sort slots of a query, checked where a batch is planned (tsgpu.hip's plan_range and the pre-scan of its device-plan twin, tsgpu_groupby.inc.h, and
+// the vector / hybrid entry points, which refuse the kinds beyond TSGPU_SORT_VECTOR_DISTANCE)
+namespace tsgpu {
+inline bool sort_kind_reads_column(uint8_t kind) { return kind == TSGPU_SORT_INT64_COLUMN || (kind >= TSGPU_SORT_INT64_COLUMN_MISSING_FIRST && kind <= TSGPU_SORT_STRING_RANK_FLIP); }
+inline bool sort_kind_reads_key(uint8_t kind) { return kind == TSGPU_SORT_EVAL || sort_kind_reads_column(kind); }
+// TSGPU_OK, 400 (a TSGPU_SORT_EVAL slot whose handle is not live) or 501 (a kind / column / order this path does not serve; two _eval slots). allow_vdist: the flat
+// vector branch; refuse_keys: an entry point that does not serve kinds >= TSGPU_SORT_EVAL (so does every context that is a member of a tsgpu_group: a key is
+// one context's). bytes_per_id (nullable): what the slots read per ranked document — 8 per column value, 1 per dense-key byte, 4 x probes per sparse key.
+inline int check_sort_slots(tsgpu_ctx* ctx, const tsgpu_sort_by* sort, uint32_t n_sort, bool allow_vdist, bool refuse_keys, uint64_t* bytes_per_id) {
+    uint32_t n_eval = 0;
+    uint64_t bytes = 0;
+    int rc = TSGPU_OK;
+    for (uint32_t s = 0; s < n_sort; s++) {
+        const uint8_t kind = sort[s].kind;
+        if (kind > TSGPU_SORT_STRING_RANK_FLIP) return TSGPU_ERR_UNSUPPORTED;
+        if (kind == TSGPU_SORT_VECTOR_DISTANCE && !allow_vdist) return TSGPU_ERR_UNSUPPORTED;
+        if (kind >= TSGPU_SORT_EVAL && (refuse_keys || ctx->group_member.load(std::memory_order_relaxed) > 0)) return TSGPU_ERR_UNSUPPORTED;
+        if (sort[s].order != 1 && sort[s].order != -1) return TSGPU_ERR_UNSUPPORTED;
+        if (sort_kind_reads_column(kind)) {
+            if (sort[s].column >= ctx->columns.size()) return TSGPU_ERR_UNSUPPORTED;
+            bytes += 8;
+        }
+        if (kind == TSGPU_SORT_EVAL) {
+            n_eval++;
+            std::lock_guard<std::mutex> lk(ctx->sk_mu);
+            if (sort[s].column >= ctx->sort_keys.size() || !ctx->sort_keys[sort[s].column].live) rc = TSGPU_ERR_INVALID;
+            else {
+                const SortKeyHost& k = ctx->sort_keys[sort[s].column];
+                uint32_t probes = 1;
+                for (uint64_t n = k.n_ids / std::max<uint32_t>(k.n_expr, 1); n > 1; n >>= 1) probes++;
+                bytes += k.dense ? 1 : 4ull * probes * k.n_expr;
+            }
+        }
+    }
+    if (n_eval > 1) return TSGPU_ERR_UNSUPPORTED;          // (the reference shares one cursor vector between them, src/index.cpp:5809-5811)
+    if (bytes_per_id) *bytes_per_id = bytes;
+    return rc;
+}
+}  // namespace tsgpu
 
 // ---- device-side halves of tsgpu_group's exchange (tsgpu_group.hip orchestrates; kernels: kw_kernels.hip.h / vec_kernels.hip.h).
 // All of them ENQUEUE on `s` and do not synchronise. A keyword exchange block = n_q records of k * words + 3 u64 (KwShardIn::packed),

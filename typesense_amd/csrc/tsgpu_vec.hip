@@ -1311,6 +1311,14 @@ static int vector_search_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu
     if (n_q == 0) { if (ids_out) { *ids_out = new (std::nothrow) tsgpu_id_lists; if (*ids_out) (*ids_out)->begin.assign(1, 0); } return ok(); }
     if (p->n_sort > 3) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch: more than 3 sort keys");
     if ((p->n_filter && !p->filter_ids) || (p->n_excluded && !p->excluded_ids)) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch: id array is NULL");
+    for (uint32_t j = 0; j < p->n_sort; j++) if (p->sort[j].kind >= TSGPU_SORT_EVAL) {
+        // the reference walks the k-NN hits in distance order with the _eval branch's forward-only cursor (src/index.cpp:3675, :5817): not served here, every query reports 501
+        if (!out->n_hits || !out->status) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch: missing output arrays");
+        if (out->mem != TSGPU_MEM_HOST) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vector_search_batch: sort kinds >= TSGPU_SORT_EVAL are not served by the vector entry points");
+        for (uint32_t i = 0; i < n_q; i++) { out->status[i] = TSGPU_ERR_UNSUPPORTED; out->n_hits[i] = 0; if (out->num_matched) out->num_matched[i] = 0; }
+        if (ids_out) { *ids_out = new (std::nothrow) tsgpu_id_lists; if (*ids_out) (*ids_out)->begin.assign((size_t)n_q + 1, 0); }
+        return ok();
+    }
     const bool filter_by_provided = p->filter_by_provided || p->n_filter;
     if (filter_by_provided && p->n_filter != 0 && (uint64_t)p->n_filter < p->flat_search_cutoff) {     // :3664 (an empty filter never gets here: the search returns before)
         if (!out->keys || !out->scores || !out->n_hits || !out->status) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch: missing output arrays");
@@ -1479,7 +1487,10 @@ int tsgpu_hybrid_fuse_batch(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, const
             for (;;) {
                 const uint32_t q = next.fetch_add(1);
                 if (q >= n_queries) break;
-                const int32_t st = kw_hits->status ? kw_hits->status[q] : TSGPU_OK;
+                int32_t st = kw_hits->status ? kw_hits->status[q] : TSGPU_OK;
+                // host_sort_scores re-scores the vector hits in DISTANCE order; the reference's _eval cursor only moves forward there (src/index.cpp:4115, :5817): the
+                // sort kinds >= TSGPU_SORT_EVAL are not served by the hybrid entry points
+                for (uint32_t j = 0; j < queries[q].n_sort && j < TSGPU_MAX_SORT_KEYS && st == TSGPU_OK; j++) if (queries[q].sort[j].kind >= TSGPU_SORT_EVAL) st = TSGPU_ERR_UNSUPPORTED;
                 out->status[q] = st;
                 if (out->search_cutoff) out->search_cutoff[q] = kw_hits->search_cutoff ? kw_hits->search_cutoff[q] : 0;
                 if (st != TSGPU_OK) { out->n_hits[q] = 0; if (out->num_matched) out->num_matched[q] = 0; continue; }

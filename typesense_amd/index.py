@@ -146,9 +146,13 @@ class GpuIndex:
         B.check(self.L, self.L.tsgpu_create(device, C.byref(h)))
         self.h = h
         self.vec_dim = {}
+        self._sort_keys = set()
 
     def close(self):
         if getattr(self, "h", None):
+            for handle in list(getattr(self, "_sort_keys", ())):
+                self.L.tsgpu_sort_key_destroy(self.h, handle)
+            self._sort_keys = set()
             self.L.tsgpu_destroy(self.h)
             self.h = None
 
@@ -210,6 +214,24 @@ class GpuIndex:
 
     def set_num_docs(self, n):
         self._ck(self.L.tsgpu_set_num_docs(self.h, n))
+
+    def sort_key_create_eval(self, id_lists, scores):
+        """the key of an `_eval(...)` sort slot (B.SORT_EVAL): id_lists[e] = ascending unique seq_ids expression e matches, scores[e] its score.
+        Returns the handle the slot carries as its column; the lists are uploaded here, once."""
+        lists = [_u32(a) for a in id_lists]
+        sc = np.ascontiguousarray(scores, dtype=np.int64)
+        if len(lists) != sc.size:
+            raise ValueError("one score per expression")
+        ptrs = (C.c_void_p * max(len(lists), 1))(*[a.ctypes.data if a.size else None for a in lists])
+        n = _u32([a.size for a in lists])
+        handle = C.c_uint16(0)
+        self._ck(self.L.tsgpu_sort_key_create_eval(self.h, C.cast(ptrs, C.c_void_p), _vp(n), _vp(sc), len(lists), C.byref(handle)))
+        self._sort_keys.add(int(handle.value))
+        return int(handle.value)
+
+    def sort_key_destroy(self, handle):
+        self._ck(self.L.tsgpu_sort_key_destroy(self.h, int(handle)))
+        self._sort_keys.discard(int(handle))
 
     def commit(self):
         self._ck(self.L.tsgpu_commit(self.h))
