@@ -149,6 +149,23 @@ public:
         return true;
     }
 
+    // n appends in one decode / encode: the state after append(vals[0]) .. append(vals[n - 1]) (a document of tens of thousands of
+    // positions would otherwise re-encode the block once per position)
+    void append_all(const uint32_t* vals, size_t n) {
+        if (n == 0) return;
+        uint32_t* arr = uncompress(length + (uint32_t)n);
+        for (size_t i = 0; i < n; i++) {
+            arr[length + i] = vals[i];
+            if (vals[i] < min) min = vals[i];
+            if (vals[i] > max) max = vals[i];
+        }
+        const uint32_t total = length + (uint32_t)n;
+        uint32_t lo = arr[0], hi = arr[0];
+        for (uint32_t i = 1; i < total; i++) { lo = std::min(lo, arr[i]); hi = std::max(hi, arr[i]); }
+        encode(arr, total, lo, required_bits(hi - lo));
+        delete[] arr;
+    }
+
     bool insert(size_t index, const uint32_t* values, size_t num_values) {  // :62-84
         if (index >= length) return false;
         uint32_t* arr = uncompress(length + (uint32_t)num_values);

@@ -93,6 +93,25 @@ static void test_arrays() {
         arr.remove_index(5, 8);
         CHECK_EQ(arr.getLength(), 3000u); CHECK_EQ(arr.at(5), ref[5]);
     }
+    {   // array::append_all (the block upsert's bulk form) leaves the state of one append() per value: bytes, length, min, max
+        std::mt19937 rng(11);
+        const uint32_t spans[5] = {1, 2, 300, 70000, 0xFFFFFFFFu};
+        bool same = true;
+        for (int round = 0; round < 40; round++) {
+            array one, all;
+            const uint32_t span = spans[round % 5], base = round % 3 ? rng() % 1000 : 0;
+            for (int part = 0; part < 3; part++) {                    // onto an empty array, then onto a filled one; a part of 0 values
+                std::vector<uint32_t> vals(part == 1 && round % 4 == 0 ? 0 : 1 + rng() % 400);
+                for (auto& v : vals) v = span == 0xFFFFFFFFu ? (uint32_t)rng() : base + rng() % span;
+                if (part == 2 && !vals.empty()) vals.back() = 0;       // the last-token flag
+                for (uint32_t v : vals) one.append(v);
+                all.append_all(vals.data(), vals.size());
+                same = same && one.getLength() == all.getLength() && one.getMin() == all.getMin() && one.getMax() == all.getMax() &&
+                       one.getSizeInBytes() == all.getSizeInBytes() && memcmp(one.raw(), all.raw(), one.getSizeInBytes()) == 0;
+            }
+        }
+        CHECK(same);
+    }
     {   // bit-width edges: all equal (0 bits), full 32-bit range
         sorted_array a;
         uint32_t same[4] = {9, 9, 9, 9};

@@ -74,7 +74,7 @@ public:
                 ids.append(id);
                 uint32_t curr_index = offsets.getLength();
                 offset_index.append(curr_index);
-                for (uint32_t p : positions) offsets.append(p);
+                offsets.append_all(positions.data(), positions.size());      // = offsets.append(p) for every p
                 return 1;
             }
             uint32_t id_index = ids.indexOf(id);
