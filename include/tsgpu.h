@@ -141,7 +141,7 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * server (4 = SSE, what the reference's stock build flags give; 8 = -mavx; 16 = -mavx512f): hnswlib's InnerProductSpace accumulates
  * element i in lane i % lanes and adds the lanes left to right, so the bits of a distance depend on it;
  * "vec_prefilter" = 1 (default): bf16 bracket scan + exact fp32 re-score of the survivors, 0: fp32 MFMA scan of every row
- * (identical result sets either way), "vec_count_rescored" = 1: keep the vec_rescored_rows counter (costs one sync);
+ * (identical result sets either way), "vec_count_rescored" = 1: keep the vec_rescored_rows and vec_candidate_rows counters (costs two syncs);
  * micro-batcher: "batch_max_queries" = calls with at most this many queries are coalesced with concurrent callers (default 64,
  * 0 = never), "batch_window_us" = how long a round's leader waits for the other threads that are inside the entry point to
  * park (default 10: a lane that is free should not idle; while every lane is busy callers keep parking and the rounds size
@@ -173,7 +173,8 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * "hnsw_visited_max_gib" (default 64, 1..128: 2 bytes x rows x concurrent queries — 41 GB for 2048 queries at 10M rows) */
 int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
 /* introspection counters (tests / bench): "vec_overflow_rounds", "vec_prefilter_groups", "vec_prefilter_fallbacks",
- * "vec_rescored_rows", "kw_last_hit_groups" (find+score groups of the last keyword batch, 0 = fused), "kw_last_hit_records",
+ * "vec_rescored_rows", "vec_candidate_rows" (rows of the last bracket group that reached the exact re-score / that passed the scan's tile-level bound),
+ * "kw_last_hit_groups" (find+score groups of the last keyword batch, 0 = fused), "kw_last_hit_records",
  * "batch_rounds" / "batch_coalesced_calls" (micro-batcher: rounds executed / calls they served; "gb_batch_rounds" / "gb_batch_coalesced_calls": of grouped calls), host phase totals in us over all
  * keyword batches ("kw_batches", "kw_plan_us", "kw_upload_us", "kw_launch_us", "kw_wait_us", "kw_book_us", "batch_exec_us",
  * "batch_scatter_us") and over all coalesced calls ("kw_queue_us" = parked -> its round starts, "kw_wake_us" = results ready ->

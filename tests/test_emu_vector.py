@@ -1,6 +1,10 @@
 """Vector / hybrid path (vec_kernels.hip.h, tsgpu_vec.hip) on the CPU under the SIMT emulator (MFMA modelled as
 the k-ordered fmaf chain of v_mfma_f32_32x32x2_f32), against the oracle's exact flat scan.
-Tolerance: distances within 1e-5 relative (north_star); label sets identical; ties broken by smaller label."""
+Two kinds of comparison. The bf16 bracket path (default) re-scores its survivors in hnswlib's own summation order: the tests that pin it
+(_check_knn_bits and the tests written around it: test_prefilter_*, test_every_summation_order_*, test_one_huge_tight_cluster_*,
+test_vector_branch_flat_and_k_cut_*, test_edge_cases_*, the HNSW traversals; tests/test_emu_vector_values.py) compare labels IN ORDER and
+distance BITS, no tolerance. _check_knn and the hybrid / Topster tests predate it and also cover the fp32 MFMA scan (vec_prefilter = 0, the
+fallback), whose summation order is its own: distances within 1e-5 relative (north_star), label sets identical, ties broken by smaller label."""
 import ctypes as C
 
 import numpy as np
@@ -237,11 +241,21 @@ def test_prefilter_brackets_prune_but_never_drop_a_neighbour():
     _check_knn_bits(g, orc, Q, k)
     assert g.counter("vec_prefilter_fallbacks") == 0
     assert 3 * k <= g.counter("vec_rescored_rows") < 3 * n // 4        # pruned, not everything re-scored
-    # non-finite data never poisons the bounds: an inf row and a NaN row are re-scored like everyone else
+    # non-finite data never poisons the bounds: an inf row and a NaN row are re-scored like everyone else, and every other row keeps the oracle's rank
+    # (the oracle's place for a NaN distance is unspecified: it gets every row but that one; vector_values_common.finite_ranks_equal)
+    from tests import vector_values_common as V
     bad = X[:2].copy(); bad[0, 3] = np.inf; bad[1, 7] = np.nan
     g.vec_upsert(1, np.array([10, 11], np.uint64), bad)
+    X2 = X.copy(); X2[10] = bad[0]
+    keep = labels != 11
+    orc2 = O.OracleIndex(1, 1)
+    orc2.vec_init(dim, O.METRIC_IP)
+    orc2.vec_add(labels[keep].astype(np.uint32), X2[keep])
     dist, lab, cnt = g.vec_knn_batch(1, Q[1:2], k)
     assert cnt[0] == k
+    V.finite_ranks_equal(g, orc2, Q, k, (11,), "inf row 10, NaN row 11")
+    assert g.counter("vec_prefilter_fallbacks") == 0
+    orc2.close()
     g.close()
 
 

@@ -586,6 +586,7 @@ struct tsgpu_ctx {
     int fuse_threads = 32;                            // host threads of the hybrid rank fusion (option "fuse_threads")
     uint64_t hnsw_last_expansions = 0, hnsw_last_distances = 0;   // last HNSW batch: candidates expanded / distances computed at layer 0 (all queries)
     uint64_t vec_rescored_rows = 0;                  // survivors re-scored in fp32 by the last prefilter group (sum over its queries; 0 unless vec_count_rescored)
+    uint64_t vec_candidate_rows = 0;                 // rows past the tile-level bound in that group's last scan round (sum over slabs and queries; same switch)
     uint32_t vec_count_rescored = 0;
     uint64_t vec_prefilter_fallbacks = 0;            // query groups the bf16 bracket could not separate (ran on the fp32 scan)
     uint64_t vec_overflow_rounds = 0;                // pass-2 repeats caused by candidate overflow (introspection)

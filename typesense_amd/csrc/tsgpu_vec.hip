@@ -188,7 +188,7 @@ static int knn_group(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n
 }
 
 
-// safety inflation of the stored row norms (fp32 sum-of-squares error << 2^-10)
+// safety inflation of the stored row norms (fp32 sum-of-squares error << 2^-10; sums too small to trust are stored as +inf, vec_to_bf16_kernel)
 static const float VEC_NORM_INFLATE = 1.0f + 1.0f / 1024.0f;
 // error-radius constant of the bf16 bracket (vec_kernels.hip.h): (2u + u^2) with u = 2^-8, + dim * 2^-21 for the two fp32
 // accumulations, + 1 %
@@ -339,6 +339,12 @@ static int knn_group_prefilter(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
         TSGPU_HIP_TRY(hipStreamSynchronize(s));
         ctx->vec_rescored_rows = 0;
         for (uint32_t i = 0; i < n_q; i++) ctx->vec_rescored_rows += sc[i];
+        // ... and how many passed the scan's tile-level bound (cq * tile_nmax) in its last round: what a stale or dominated tile maximum inflates
+        sc.resize((size_t)n_slabs * n_q);             // n_slabs: geometry(n_tiles, 256) above = what launch_scan(a, 256) computed as a.n_slabs for the same n_ord
+        TSGPU_HIP_TRY(hipMemcpyAsync(sc.data(), f->d_cand_cnt.p, sc.size() * 4, hipMemcpyDeviceToHost, s));
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        ctx->vec_candidate_rows = 0;
+        for (uint32_t c : sc) ctx->vec_candidate_rows += c;
     }
     if (record_events) TSGPU_HIP_TRY(hipEventRecord(ctx->ev[5], s));
     return TSGPU_OK;

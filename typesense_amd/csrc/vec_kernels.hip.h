@@ -417,8 +417,23 @@ __global__ void vec_normalize_rows_kernel(float* __restrict__ X, uint32_t n_rows
 // survive that test twice (L1 from a strided sample, then L2 from the survivors themselves; ~1.1-3 k rows per query
 // remain) are re-scored EXACTLY in fp32 with the reference's own summation order (hnswlib InnerProductSpace: 16
 // accumulator lanes, multiply and add rounded separately, sequential horizontal add — bit-identical distances), and
-// the final k are selected from those exact keys. Exactness therefore never depends on bf16 rounding, on the MFMA's
-// internal accumulation order, or on the data distribution (overflowing candidate lists tighten L1 and re-scan).
+// the final k are selected from those exact keys.
+// What is guaranteed, for EVERY finite input: a row is dropped only if its rounded DISTANCE d = fl(1 - s^) — what the reference ranks
+// on, ties broken by the smaller label — is STRICTLY greater than that of k other rows. Two things carry that beyond "|s~ - s^| <= e":
+//  (1) The survivor tests run in distance space. fl(1 - s) is monotone but not injective: once |s| is far below ulp(1) (entries of a few
+//      1e-4 on both sides at dim 64) rows whose score is provably below L still TIE the k-th distance, and the label decides. So a bound
+//      L (L1, L2) is replaced by T(L) = the smallest float u with fl(1 - u) <= fl(1 - L) (vec_dist_floor): k rows have s^ >= L, hence
+//      d <= fl(1 - L); a row with s~ + e < T(L) has s^ < T(L), hence d > fl(1 - L) >= the k-th distance. T(L) <= L differs from L by at
+//      most half an ulp of max(1, |L|): nothing against e on ordinary data. The scan kernel reads T(L1) where it read L1; its code is unchanged.
+//  (2) A norm fp32 cannot form is never used. For |x| <~ 3e-23 every square underflows (sum = 0), below ~1e-19 the squares are subnormal
+//      and the sum loses bits: e would collapse to its floor although the bf16 error is 2^-7 of the score. A row or query with
+//      0 < sum x^2 < 2^-80 (||x|| < 2^-40) gets the norm +inf = UNBOUNDED, like a non-finite one (next paragraph). At and above that
+//      threshold the sum is exact to dim * 2^-69 relative, cq * ||x|| >= 2^-87 is a normal number, and what products that underflow in
+//      either scan can lose (<= dim * 2^-126 * the other side's entry) is far inside e. The overflow side (sum = inf) is non-finite already.
+// Hence the result does not depend on bf16 rounding, on the MFMA's internal accumulation order, or on the value distribution; what the
+// distribution decides is the COST: overflowing candidate lists tighten L1 and re-scan, and when more rows than the survivor arena holds
+// sit inside the bracket or tie the k-th distance (all-equal distances, collections of rows with ||x|| < 2^-40, ...) the group runs on the
+// fp32 scan, whose (distance, row) keys converge on any input.
 // Non-finite scores / norms get lb = -inf, ub = +inf: always re-scored, never used as a bound.
 typedef __bf16 vec_bf16x8 __attribute__((ext_vector_type(8)));
 static const int VEC_HKC = 64;                  // bf16 K chunk per LDS step = 128 bytes per row, same LDS geometry as the fp32 scan
@@ -428,6 +443,21 @@ static const uint64_t VEC_ENT_INVALID = 0xFFFFFFFFFFFFFFFFull;
 __device__ inline uint32_t f32_desc_key(float f) { return ~f32_ord(f); }
 __device__ inline float desc_key_f32(uint32_t k) { return ord_f32(~k); }
 __device__ inline bool f32_finite(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
+
+// T(L) = the smallest float u with fl(1 - u) <= fl(1 - L) (see (1) above): bisection over the order-preserving integer image of the
+// floats, 32 steps of one subtraction each; called by one thread per query. -inf ("no bound") and +inf map to themselves.
+__device__ inline float vec_dist_floor(float L) {
+    if (!f32_finite(L)) return L;
+    const float D = 1.0f - L;
+    uint32_t lo = f32_ord(-3.4028234663852886e38f), hi = f32_ord(L);      // invariant: fl(1 - ord_f32(hi)) <= D
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (1.0f - ord_f32(mid) <= D) hi = mid; else lo = mid + 1;
+    }
+    return ord_f32(hi);
+}
+// sums of squares below this are not trusted as a norm (see (2) above): 2^-80
+static const float VEC_SS_MIN = 8.271806125530277e-25f;
 
 // fp32 -> bf16, round to nearest even; finite values that would round to infinity saturate to the largest finite
 // bf16 (relative error still <= 2^-8), NaN stays NaN, +-inf stays +-inf
@@ -453,7 +483,7 @@ __device__ inline size_t vec_xh_index(uint32_t row, uint32_t k, uint32_t n_chunk
 __device__ inline size_t vec_qh_index(uint32_t q, uint32_t k, uint32_t n_pad) { return ((size_t)(k >> 6) * n_pad + q) * VEC_HKC + (k & 63); }
 
 // one wave per row: bf16 copy (zero padded to dimp, a multiple of 64) in the tiled layout + norm_out[row] = scale * ||x||_2
-// (fp32 sum of squares, `scale` carries the safety inflation / the query-side constant c). q_pad == 0: row layout, else
+// (fp32 sum of squares; +inf when it underflows, `scale` carries the safety inflation / the query-side constant c). q_pad == 0: row layout, else
 // query layout with n_pad = q_pad.
 __global__ __launch_bounds__(256) void vec_to_bf16_kernel(const float* __restrict__ X, uint16_t* __restrict__ Xh, float* __restrict__ norm_out,
                                                            uint32_t row0, uint32_t n_rows, uint32_t dim, uint32_t dimp, float scale, uint32_t q_pad) {
@@ -464,16 +494,21 @@ __global__ __launch_bounds__(256) void vec_to_bf16_kernel(const float* __restric
     const float* __restrict__ x = X + (size_t)r * dim;
     const uint32_t n_chunks = dimp / VEC_HKC;
     float ss = 0.0f;
+    bool nz = false;
     for (uint32_t k = 2 * lane; k < dimp; k += 128) {
         const float a = k < dim ? x[k] : 0.0f, b = k + 1 < dim ? x[k + 1] : 0.0f;
         ss = fmaf(a, a, ss);
         ss = fmaf(b, b, ss);
+        nz |= (a != 0.0f) | (b != 0.0f);
         const size_t at = q_pad ? vec_qh_index(r, k, q_pad) : vec_xh_index(r, k, n_chunks);
         *(uint32_t*)(Xh + at) = f32_to_bf16_bits(a) | (f32_to_bf16_bits(b) << 16);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    if (lane == 0) norm_out[r] = sqrtf(ss) * scale;
+    // a non-zero vector whose squares underflow has no usable norm: +inf = unbounded (always re-scored, never a bound). An all-zero
+    // vector keeps the exact norm 0 (its scores are exactly 0 in both scans). NaN / inf sums pass through as before.
+    const bool tiny = __ballot(nz) != 0 && ss < VEC_SS_MIN;
+    if (lane == 0) norm_out[r] = tiny ? __uint_as_float(0x7F800000u) : sqrtf(ss) * scale;
 }
 
 // per 128-row tile: max of the row norms (+inf if any is NaN / inf) — the scan epilogue's cheap bound
@@ -786,8 +821,10 @@ __global__ __launch_bounds__(VEC_HTHREADS) void vec_hscan_kernel(VecHScanArgs a)
                     const uint32_t gq = q0 + col;
                     const float e = cqv[cb] * nmax + 1e-30f;             // >= every row's error radius in this tile
                     if (a.mode == 0) {
-                        // keep a row iff its upper bound reaches L1: !(sc + e < L1), tested as !(sc < L1 - e) — the 1 % slack
-                        // inside c dwarfs the rounding of that subtraction. Non-finite rows / queries have e = inf or NaN, so
+                        // keep a row iff its upper bound reaches T = L1[q] (= T(L1), distance space): !(sc + e < T), tested as !(sc < thr),
+                        // thr = fl(T - e). Sound whatever that subtraction rounds to, also where e << ulp(T) (the distance-tie regime): rounding
+                        // is monotone, so a float sc < fl(T - e) is <= the real T - e; the true radius e' is below e (1 % slack, floor), hence
+                        // s^ <= sc + e' < T, and a float below T has a distance above fl(1 - L1). Non-finite rows / queries have e = inf or NaN, so
                         // thr is -inf / NaN and every compare below passes: nothing non-finite is ever rejected.
                         const float thr = L1v[cb] - e;
                         float amax = acc[0][cb][0];
@@ -875,7 +912,7 @@ __device__ inline uint32_t block_kth_smallest_u32(uint32_t n, uint32_t k, KeyFn 
     return prefix;
 }
 
-// sample pass -> L1[q] = k-th largest group maximum of the sample's lower bounds (-inf when fewer than k groups hold a row)
+// sample pass -> L1[q] = T(k-th largest group maximum of the sample's lower bounds) (-inf when fewer than k groups hold a row)
 __global__ __launch_bounds__(VEC_THREADS) void vec_thresh_kernel(const uint32_t* __restrict__ gmax, size_t stride, uint32_t n, uint32_t k, float* __restrict__ L1) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_state[2], s_valid;
@@ -890,11 +927,11 @@ __global__ __launch_bounds__(VEC_THREADS) void vec_thresh_kernel(const uint32_t*
     const bool enough = s_valid >= k;
     __syncthreads();
     const uint32_t kk = block_kth_smallest_u32(n, k, [&](uint32_t i) { return keys[i]; }, hist, s_state);
-    if (t == 0) L1[q] = enough ? desc_key_f32(kk) : __uint_as_float(0xFF800000u);
+    if (t == 0) L1[q] = enough ? vec_dist_floor(desc_key_f32(kk)) : __uint_as_float(0xFF800000u);       // T(L1): the scan tests in distance space
 }
 
-// one workgroup per query. Gathers the query's candidate segments (one per slab), L2 = k-th largest lower bound
-// s~ - c|q||x_row| among them (exact per-row norms), survivors (upper bound >= L2) -> surv rows for the exact re-score.
+// one workgroup per query. Gathers the query's candidate segments (one per slab), L2 = T(k-th largest lower bound
+// s~ - c|q||x_row| among them) (exact per-row norms; T = vec_dist_floor), survivors (upper bound >= L2) -> surv rows for the exact re-score.
 // The lower-bound keys of the gathered entries live in LDS for the radix passes (VEC_REFINE_LCAP entries); a query with more
 // candidates (its k-th neighbour sits in a cluster of tens of thousands of near-ties) spills the rest to its slice of a global list
 // (gkeys, gcap entries per query; the radix passes then read both).
@@ -957,7 +994,7 @@ __global__ __launch_bounds__(VEC_THREADS) void vec_refine_kernel(const uint64_t*
     const bool enough = s_valid >= k;
     __syncthreads();
     const uint32_t kk = block_kth_smallest_u32(n_held, k, key_at, hist, s_state);
-    const float L2 = enough ? desc_key_f32(kk) : NEG_INF;
+    const float L2 = enough ? vec_dist_floor(desc_key_f32(kk)) : NEG_INF;        // T(L2): survivors are tested, and L1 is raised, in distance space
     if (over) {
         if (t == 0) {
             const bool raised = L2 > L1[q];
