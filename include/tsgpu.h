@@ -249,6 +249,14 @@ uint32_t tsgpu_term_num_ids(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id)
  * tsgpu_term_num_ids / *n_offsets (call once with NULL buffers to size). */
 int tsgpu_term_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, uint32_t* ids,
                         uint32_t* offset_index, uint32_t* offsets, uint32_t* n_offsets);
+/* the block layout of a committed list as the kernels read it (tests: which states an incremental commit left behind), read back from the
+ * device: per block records[4 b ..] = its BlockIds {first_id, last_id, ids_woff, n_ids | ids_bits << 16} and arena_pos[b] = the word
+ * position of its ids in the ids arena (ListDesc::ids_base + ids_woff: a block whose position does not follow its predecessor's words is
+ * a break); *list_flags = ListDesc::flags (TSGPU_LIST_HAS_BREAKS), *dir_slot = ListDesc::dir_slot (0: no id directory). At most `cap`
+ * blocks are written; *n_blocks gets the list's block count (call once with cap = 0 to size). 404 when the term is not committed. */
+#define TSGPU_LIST_HAS_BREAKS 1u
+int tsgpu_term_blocks_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, uint32_t* records, uint64_t* arena_pos, uint32_t cap,
+                               uint32_t* n_blocks, uint32_t* list_flags, uint32_t* dir_slot);
 
 /* ------------------------------------------------------------------ keyword search (seam B1) */
 typedef struct tsgpu_sort_by {

@@ -13,6 +13,7 @@ SORT_KEY_SLOTS = 4096
 METRIC_IP, METRIC_COSINE = 0, 1
 MAX_SCORE, MAX_WEIGHT, SUM_SCORE = 0, 1, 2
 MAX_QUERY_TOKENS = 10
+LIST_HAS_BREAKS = 1
 FLT_MAX = 3.4028234663852886e38
 
 
@@ -127,7 +128,7 @@ class HostCollectivesC(C.Structure):
 EXPORTS = [
     "tsgpu_abi_version", "tsgpu_create", "tsgpu_destroy", "tsgpu_last_error", "tsgpu_set_stream", "tsgpu_set_option", "tsgpu_get_counter", "tsgpu_device_bytes",
     "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_destroy", "tsgpu_commit",
-    "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
+    "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_term_blocks_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
     "tsgpu_keyword_search_batch_ids", "tsgpu_keyword_search_grouped_batch", "tsgpu_keyword_search_grouped_candidates_batch", "tsgpu_id_lists_count", "tsgpu_id_lists_ids", "tsgpu_id_lists_free", "tsgpu_facet_set", "tsgpu_facet_count_batch", "tsgpu_facet_count_grouped_batch", "tsgpu_facet_range_count_batch", "tsgpu_facet_stats_batch", "tsgpu_facet_value_set", "tsgpu_facet_value_count_batch",
     "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch",
     "tsgpu_vec_hnsw_load", "tsgpu_vec_hnsw_enable", "tsgpu_vec_hnsw_build", "tsgpu_vec_hnsw_export", "tsgpu_vec_hnsw_search_batch", "tsgpu_vec_distances", "tsgpu_ip_distance", "tsgpu_vector_search_batch", "tsgpu_vector_search_batch_ids", "tsgpu_hybrid_search_batch", "tsgpu_hybrid_fuse_batch", "tsgpu_keyword_aux_scores", "tsgpu_merge_shard_hits", "tsgpu_merge_shard_hits_device", "tsgpu_last_timings", "tsgpu_last_aux_timings", "tsgpu_kw_last_touched", "tsgpu_kw_lists_footprint",
@@ -181,6 +182,7 @@ def lib(path=None):
     L.tsgpu_term_num_ids.argtypes = [vp, u32, u32]
     L.tsgpu_term_num_ids.restype = u32
     L.tsgpu_term_download.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(u32)]
+    L.tsgpu_term_blocks_download.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.tsgpu_keyword_search_batch.argtypes = [vp, vp, u32, C.POINTER(HitsC)]
     L.tsgpu_wildcard_search_batch.argtypes = [vp, vp, u32, C.POINTER(HitsC)]
     L.tsgpu_keyword_search_candidates_batch.argtypes = [vp, vp, vp, u32, C.POINTER(HitsC), vp, vp]

@@ -325,9 +325,10 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
             if (hit == target) { found = true; p1 = (C.base + kb) * BLOCK_IDS + pos; }
         };
         if (C.mode == 0) {
-            // every block but a list's last is full, and 16-bit wherever the list is dense: when that holds for all of a wavefront's
-            // candidates the two searches run as ONE straight-line sequence of two independent chains (candidates that dropped out
-            // search the tile's first block: harmless reads)
+            // a freshly packed list's blocks are full but the last, and 16-bit wherever the list is dense (incremental commits leave part-filled
+            // and re-widened blocks anywhere in a list: those take slot_search below): when every candidate of a wavefront meets a full 16-bit
+            // block the two searches run as ONE straight-line sequence of two independent chains (candidates that dropped out search the
+            // tile's first block: harmless reads)
             constexpr uint32_t FULL16 = (16u << 16) | (uint32_t)BLOCK_IDS;
             const bool fast = (done0 || nb0 == FULL16) && (done1 || nb1 == FULL16);
             if (KW_F2_FAST && __ballot(fast ? 0 : 1) == 0) {

@@ -800,4 +800,27 @@ int tsgpu_term_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, uin
     return ok();
 }
 
+int tsgpu_term_blocks_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, uint32_t* records, uint64_t* arena_pos, uint32_t cap,
+                               uint32_t* n_blocks, uint32_t* list_flags, uint32_t* dir_slot) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    (void)hipSetDevice(ctx->device);
+    const std::shared_ptr<const Snapshot> sn = ctx->snapshot();     // the committed snapshot, like tsgpu_term_download
+    const uint32_t h = sn->find_handle(field_id, term_id);
+    if (h == 0xFFFFFFFFu) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_term_blocks_download: term not in the committed snapshot");
+    const ListDesc d = sn->h_lists[h];
+    if (n_blocks) *n_blocks = d.n_blocks;
+    if (list_flags) *list_flags = d.flags;
+    if (dir_slot) *dir_slot = d.dir_slot;
+    const uint32_t n = std::min(cap, d.n_blocks);
+    if (n == 0 || (!records && !arena_pos)) return ok();
+    try {
+        static_assert(sizeof(BlockIds) == 16, "records: four words per block");
+        std::vector<BlockIds> bi(n);
+        TSGPU_HIP_TRY(hipMemcpy(bi.data(), sn->ar->blk_ids.as<BlockIds>() + d.blk_base, (size_t)n * sizeof(BlockIds), hipMemcpyDeviceToHost));
+        if (records) memcpy(records, bi.data(), (size_t)n * sizeof(BlockIds));
+        if (arena_pos) for (uint32_t b = 0; b < n; b++) arena_pos[b] = d.ids_base + bi[b].ids_woff;
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_term_blocks_download: host allocation failed"); }
+    return ok();
+}
+
 }  // extern "C"

@@ -247,6 +247,18 @@ class GpuIndex:
         self._ck(self.L.tsgpu_term_download(self.h, field_id, term_id, _vp(ids), _vp(oi), off.ctypes.data_as(C.c_void_p), C.byref(no)))
         return ids, oi, off[:no.value]
 
+    def term_blocks(self, field_id, term_id):
+        """the block layout of a committed list as the kernels read it -> dict(first_id, last_id, n_ids, ids_bits, arena_pos: one entry per block;
+        has_breaks, has_dir)"""
+        nb, flags, slot = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._ck(self.L.tsgpu_term_blocks_download(self.h, field_id, term_id, None, None, 0, C.byref(nb), C.byref(flags), C.byref(slot)))
+        rec, pos = np.zeros((max(nb.value, 1), 4), np.uint32), np.zeros(max(nb.value, 1), np.uint64)
+        self._ck(self.L.tsgpu_term_blocks_download(self.h, field_id, term_id, rec.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p), nb.value,
+                                                   C.byref(nb), C.byref(flags), C.byref(slot)))
+        rec, pos = rec[:nb.value], pos[:nb.value]
+        return dict(first_id=rec[:, 0].copy(), last_id=rec[:, 1].copy(), n_ids=(rec[:, 3] & 0xFFFF).astype(np.int64), ids_bits=(rec[:, 3] >> 16).astype(np.int64),
+                    arena_pos=pos.astype(np.int64), has_breaks=bool(flags.value & B.LIST_HAS_BREAKS), has_dir=slot.value != 0)
+
     def device_bytes(self):
         return self.L.tsgpu_device_bytes(self.h)
 
