@@ -40,6 +40,18 @@ int refresh_column_table(tsgpu_ctx* ctx) {
     return TSGPU_OK;
 }
 
+// lays 64-byte-aligned pieces one behind the other (the plan image, the device planner's buffers): place(bytes) -> offset
+struct Placer { size_t bytes = 0; size_t operator()(size_t b) { const size_t at = (bytes + 63) & ~(size_t)63; bytes = at + b; return at; } };
+// the hit buffer's budget in records of rec_bytes (options kw_hit_buffer_records / kw_hit_buffer_mb)
+uint64_t hit_budget_records(const tsgpu_ctx* ctx, size_t rec_bytes) { return ctx->kw_hit_buffer_records ? ctx->kw_hit_buffer_records : ((uint64_t)ctx->kw_hit_buffer_mb << 20) / rec_bytes; }
+// the Topster capacity ladder of the kernels that exist at 512, 1024 AND 2048: f(std::integral_constant<int, CAP>)
+template <class F>
+void with_cap(int cap, F&& f) {
+    if (cap == 512) f(std::integral_constant<int, 512>());
+    else if (cap == 1024) f(std::integral_constant<int, 1024>());
+    else f(std::integral_constant<int, 2048>());
+}
+
 IndexView make_view(tsgpu_ctx* ctx, const Snapshot& sn) {
     IndexView v;
     v.lists = sn.lists.as<ListDesc>();
@@ -107,21 +119,6 @@ void launch_find_score_mf(int cap, hipStream_t s, uint32_t n_work, const IndexVi
     if (cap == 512 && plain && !ids_out && !oc.n_jobs) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 512) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else hipLaunchKernelGGL((kw_score_kernel<TMAX, 1024, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
-}
-
-template <int TMAX>
-void launch_search_cap(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w,
-                       const KwPartials& part, const uint32_t* aux, uint32_t* ids_out, bool s2) {
-    if (cap == 512) launch_search<TMAX, 512>(s, n_work, v, q, w, part, aux, ids_out, s2);
-    else if (cap == 1024) launch_search<TMAX, 1024>(s, n_work, v, q, w, part, aux, ids_out, s2);
-    else launch_search<TMAX, 2048>(s, n_work, v, q, w, part, aux, ids_out, s2);
-}
-
-void launch_merge(int cap, hipStream_t s, uint32_t n_q, const KwQueryDev* q, const KwPartials& part, const KwOut& out,
-                  uint32_t* ids_out, const KwWorkItem* w, uint32_t select_min) {
-    if (cap == 512) hipLaunchKernelGGL((kw_merge_kernel<512>), dim3(n_q), dim3(KW_THREADS), 0, s, q, part, out, ids_out, w, select_min);
-    else if (cap == 1024) hipLaunchKernelGGL((kw_merge_kernel<1024>), dim3(n_q), dim3(KW_THREADS), 0, s, q, part, out, ids_out, w, select_min);
-    else hipLaunchKernelGGL((kw_merge_kernel<2048>), dim3(n_q), dim3(KW_THREADS), 0, s, q, part, out, ids_out, w, select_min);
 }
 
 }  // namespace
@@ -530,8 +527,6 @@ struct Plan {
     uint32_t max_k = 1;
     uint64_t ids_total = 0;
     uint64_t list_bytes = 0;       // 4 * sum |L_t| over the batch
-    uint64_t n_numeric_sort_q = 0;
-    uint32_t chunk_blocks = 64;
 };
 }
 
@@ -594,7 +589,6 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
     }
     static const bool plan_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
     const uint64_t tp0 = now_us();
-    P.chunk_blocks = KW_CHUNK_BLOCKS;
     P.q.resize(n_queries);
     P.status.assign(n_queries, TSGPU_OK);
     P.cutoff.assign(n_queries, 0);
@@ -607,7 +601,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
     struct PlanAcc {
         std::vector<uint32_t> aux, ordered_count_q; std::vector<KwQueryMF> mf; std::vector<KwWorkItem> flat_work;
         uint64_t fbits_words = 0, ids_total = 0, list_bytes = 0;
-        uint32_t max_k = 0, n_numeric_sort_q = 0;
+        uint32_t max_k = 0;
         bool any_deadline = false, any_s2 = false, any_aux = false, any_array = false;
         uint32_t mf_max_fields = 0;
     };
@@ -656,10 +650,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
                 // Index::search_wildcard (src/index.cpp:6616-6818): rank every filter id (every seq_id without a filter) by its sort keys
                 q.mf_index = KW_NONE;
                 q.n_sort = (uint8_t)in.n_sort;
-                for (uint32_t s = 0; s < in.n_sort; s++) {
-                    q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
-                    if (sort_kind_reads_key(in.sort[s].kind)) A.n_numeric_sort_q++;
-                }
+                for (uint32_t s = 0; s < in.n_sort; s++) { q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column; }
                 q.k = k;
                 A.max_k = std::max(A.max_k, k);
                 q.n_excl = in.n_excluded;
@@ -764,10 +755,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             q.orig_num_tokens = in.orig_num_tokens; q.is_synonym = in.is_synonym_query ? 1 : 0; q.demote_synonym = in.demote_synonym_match ? 1 : 0;
             q.n_sort = (uint8_t)in.n_sort;
             if (in.n_sort > 2) A.any_s2 = true;
-            for (uint32_t s = 0; s < in.n_sort; s++) {
-                q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
-                if (sort_kind_reads_key(in.sort[s].kind)) A.n_numeric_sort_q++;
-            }
+            for (uint32_t s = 0; s < in.n_sort; s++) { q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column; }
             q.k = k;
             A.max_k = std::max(A.max_k, k);
             q.aux_off = (uint32_t)A.aux.size();
@@ -893,7 +881,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             }
             P.ordered_count_q.insert(P.ordered_count_q.end(), A.ordered_count_q.begin(), A.ordered_count_q.end());
             P.ids_total += A.ids_total; P.fbits_words += A.fbits_words; P.list_bytes += A.list_bytes;
-            P.max_k = std::max(P.max_k, A.max_k); P.n_numeric_sort_q += A.n_numeric_sort_q;
+            P.max_k = std::max(P.max_k, A.max_k);
             P.any_deadline = P.any_deadline || A.any_deadline; P.any_s2 = P.any_s2 || A.any_s2; P.any_aux = P.any_aux || A.any_aux; P.any_array = P.any_array || A.any_array; P.mf_max_fields = std::max(P.mf_max_fields, A.mf_max_fields);
         }
     }
@@ -1013,12 +1001,11 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     }
     if (bad.load()) return TSGPU_OK;
     // device buffers: [KwQueryDev x n | one aux word | totals | six scratch arrays] in d_plan, the input records in d_plan_in
-    size_t bytes = 0;
-    auto place = [&](size_t b) { const size_t at = (bytes + 63) & ~(size_t)63; bytes = at + b; return at; };
+    Placer place;
     const size_t at_q = place((size_t)n_queries * sizeof(KwQueryDev)), at_aux = place(64), at_tot = place(sizeof(KwPlanTotals)), at_nb = place((size_t)n_queries * 4),
                  at_la = place((size_t)n_queries * 4), at_lb = place((size_t)n_queries * 4), at_cnt = place((size_t)n_queries * 4), at_ch = place((size_t)n_queries * 4),
                  at_key = place((size_t)n_queries * 8), at_fw = place((size_t)n_queries * 4), at_hb = place((size_t)n_queries * 8);
-    if ((rc = L.d_plan.reserve(bytes + 64)) || (rc = L.d_plan_in.reserve((size_t)n_queries * sizeof(KwPlanIn))) || (rc = L.h_plan_tot.reserve(2 * sizeof(KwPlanTotals)))) return rc;
+    if ((rc = L.d_plan.reserve(place.bytes + 64)) || (rc = L.d_plan_in.reserve((size_t)n_queries * sizeof(KwPlanIn))) || (rc = L.h_plan_tot.reserve(2 * sizeof(KwPlanTotals)))) return rc;
     uint8_t* const dp = (uint8_t*)L.d_plan.p;
     KwPlanTotals* const d_tot = (KwPlanTotals*)(dp + at_tot);
     KwPlanTotals* const h_tot = (KwPlanTotals*)L.h_plan_tot.p;
@@ -1044,8 +1031,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     // the hit buffer must take each table in ONE group (else the host planner's grouping / the fused kernel decide)
     for (int tb = 0; tb < 2; tb++) {
         const size_t rec_bytes = (size_t)((tb == 0 ? 3 : KW_MAX_TOKENS) + 1) * 4;
-        const uint64_t budget = ctx->kw_hit_buffer_records ? ctx->kw_hit_buffer_records : ((uint64_t)ctx->kw_hit_buffer_mb << 20) / rec_bytes;
-        if (t1.hit_blocks[tb] * (uint64_t)BLOCK_IDS > budget) return TSGPU_OK;
+        if (t1.hit_blocks[tb] * (uint64_t)BLOCK_IDS > hit_budget_records(ctx, rec_bytes)) return TSGPU_OK;
     }
     const size_t n_work = (size_t)t1.n_work[0] + t1.n_work[1];
     if ((rc = L.d_plan_work.reserve(std::max<size_t>(n_work, 1) * (sizeof(KwWorkItem) + 8) + 64))) return rc;
@@ -1057,7 +1043,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     TSGPU_HIP_TRY(hipGetLastError());
     P.status.assign(n_queries, TSGPU_OK);
     P.cutoff.assign(n_queries, 0);
-    P.max_k = std::max<uint32_t>(t1.max_k, 1); P.any_s2 = t1.any_s2 != 0; P.list_bytes = t1.list_bytes; P.n_numeric_sort_q = t1.n_numeric_sort_q;
+    P.max_k = std::max<uint32_t>(t1.max_k, 1); P.any_s2 = t1.any_s2 != 0; P.list_bytes = t1.list_bytes;
     P.any_aux = any_keys.load() != 0;                  // (a sort-key slot in the batch: the score kernels with the sort-key code)
     DP.on = true;
     DP.dq = dq; DP.dw = dw; DP.daux = (const uint32_t*)(dp + at_aux); DP.hoff = (const uint64_t*)hoff;
@@ -1353,179 +1339,446 @@ static hipError_t sleeping_wait(KwLane& L, hipStream_t s) {
     return e;
 }
 
+}  // extern "C"
+
+// ---- the keyword batch executor: kw_batch_on_lane() below runs these phases in order ----
+namespace {
+// big batches of plain single-field queries: the plan is made on the device (three small kernels, one read-back) instead of ~0.5 ms of
+// host threads; any other shape — and anything the device planner hands back — goes through plan_batch()
+bool device_plan_applies(const tsgpu_ctx* ctx, const BatchOpts& bo, bool keep_ids, uint32_t n_queries) {
+    if (bo.wildcard || bo.present_elsewhere || bo.vflat) return false;
+    // (batches that keep the matched ids: only when nobody reads the segments back per query — the candidate call marks its id sets from the device tables)
+    if (keep_ids && (bo.record_last || bo.id_lists)) return false;
+    // (not for the chained slices of a sliced host delivery: there the host plans slice i + 1 WHILE slice i runs, and a planning kernel on the
+    //  second lane would wait behind the running find kernel for a place on the chip — measured: 10.05 -> 10.18 ms per 10 000 queries)
+    if (bo.chain && !(bo.chain_index == 0 && ctx->kw_host_split_device_plan)) return false;
+    return ctx->kw_two_kernels && ctx->kw_device_plan_min_queries && n_queries >= ctx->kw_device_plan_min_queries;
+}
+
+// single-field tables (<= 3 tokens / up to 10 tokens) and multi-field tables: find + score kernels when the hit buffer fits, else the
+// fused kernel. A work item can yield at most one hit per driver id, so its segment of the hit buffer holds (blk_end - blk_begin) * 256
+// records of 1 + TMAX words; the items run in groups whose segments fit the budget.
+struct TablePlan { bool two = false; std::vector<uint64_t> hoff; std::vector<size_t> group_start{0}; uint64_t need = 0, records = 0; size_t rec_bytes = 0; };
+TablePlan group_hit_segments(const std::vector<KwWorkItem>& tab, size_t rec_bytes, uint64_t budget) {
+    TablePlan tp;
+    tp.rec_bytes = rec_bytes;
+    auto records_of = [&](size_t i) { return (uint64_t)(tab[i].blk_end - tab[i].blk_begin) * BLOCK_IDS; };
+    const size_t nws = tab.size();
+    for (size_t i = 0; i < nws; i++) { budget = std::max(budget, records_of(i)); tp.records += records_of(i); }
+    tp.hoff.resize(nws);
+    uint64_t used = 0;
+    for (size_t i = 0; i < nws; i++) {
+        const uint64_t c = records_of(i);
+        if (used + c > budget) { tp.group_start.push_back(i); used = 0; }
+        tp.hoff[i] = used; used += c; tp.need = std::max(tp.need, used);
+    }
+    tp.group_start.push_back(nws);
+    tp.two = tp.group_start.size() <= 3;          // each group drains the chip between its two kernels: beyond two groups the fused kernel wins
+    return tp;
+}
+// the four kernel tables + the wildcard table of a batch: items per table, hit-buffer groups, hit records of the batch
+struct HitTables {
+    TablePlan tp[4]; size_t n[5], first[6] = {0}; uint64_t records = 0;      // (first: a table's place in the concatenation; first[5] = all work items)
+    std::vector<uint32_t> oc_jobs[2];                                        // queries of the two multi-field tables that kw_mf_ordered_count_kernel counts
+};
+int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP, HitTables& H) {
+    const std::vector<KwWorkItem>* tabs[5] = {&P.work_small, &P.work_big, &P.work_mf_small, &P.work_mf_big, &P.work_wild};
+    for (int tb = 0; tb < 5; tb++) { H.n[tb] = DP.on && tb < 2 ? DP.n_work[tb] : tabs[tb]->size(); H.first[tb + 1] = H.first[tb] + H.n[tb]; }
+    for (int tb = 0; tb < 4; tb++) {
+        if (!H.n[tb] || !ctx->kw_two_kernels) continue;
+        TablePlan& tp = H.tp[tb];
+        const size_t rec_bytes = (size_t)((tb & 1 ? KW_MAX_TOKENS : 3) * (tb >= 2 ? KW_MAX_FIELDS : 1) + 1) * 4;
+        if (DP.on) {                                    // the device planner's two tables: one group each (it checked the budget), offsets already on the device
+            tp.two = true; tp.rec_bytes = rec_bytes; tp.group_start = {0, H.n[tb]};
+            tp.need = tp.records = DP.hit_blocks[tb] * (uint64_t)BLOCK_IDS;
+            if (int rc = L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) return rc;
+        } else {
+            tp = group_hit_segments(*tabs[tb], rec_bytes, hit_budget_records(ctx, rec_bytes));
+            if (tp.two && L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) { (void)hipGetLastError(); tp.two = false; }      // no room for the hit buffer: the fused kernel needs none
+            if (!tp.two) tp.hoff.clear();
+        }
+        H.records += tp.records;
+    }
+    // multi-field queries with filter + excluded ids: counted from the hit records of ONE find launch of their table; a table that was
+    // cut into groups or runs fused cannot serve them -> 501 for those queries (their hits are not reported)
+    for (uint32_t qi : P.ordered_count_q) {
+        const int tb = P.q[qi].n_lists <= 3 ? 0 : 1;
+        const TablePlan& tp = H.tp[2 + tb];
+        if (tp.two && tp.group_start.size() == 2) H.oc_jobs[tb].push_back(qi);
+        else if (P.status[qi] == TSGPU_OK) P.status[qi] = TSGPU_ERR_UNSUPPORTED;
+    }
+    return TSGPU_OK;
+}
+
+// the device-side tables of one batch: staging produces them, the launch, delivery and id-list phases consume them
+struct KwStaged {
+    const KwQueryDev* dq = nullptr; const KwWorkItem* dw = nullptr; const uint32_t* daux = nullptr; const KwQueryMF* mf = nullptr;
+    const uint64_t* hoff[4] = {nullptr, nullptr, nullptr, nullptr};         // per kernel table: its work items' offsets into the hit buffer
+    const KwMergeGroup* groups = nullptr; const uint32_t* oc_jobs[2] = {nullptr, nullptr};
+    KwPartials part; KwOut o; uint32_t* ids_out = nullptr;
+};
+
+// ---- the plan travels in ONE pinned staging buffer and ONE host-to-device copy (queries, work items, aux ids, multi-field
+//      descriptors, hit-record offsets): a pageable source costs a staged synchronous copy per call, five calls per batch ----
+int upload_plan_image(KwLane& L, hipStream_t s, const Plan& P, const DevPlan& DP, const std::vector<KwWorkItem>& work, const HitTables& H, KwStaged& T) {
+    Placer place;
+    const size_t at_q = place(P.q.size() * sizeof(KwQueryDev)), at_w = place(work.size() * sizeof(KwWorkItem)), at_aux = place(P.aux.size() * 4),
+                 at_mf = place(P.mf.size() * sizeof(KwQueryMF));
+    size_t at_hoff[4];
+    for (int tb = 0; tb < 4; tb++) at_hoff[tb] = place(H.tp[tb].hoff.size() * 8);
+    const size_t at_grp = place(P.groups.size() * sizeof(KwMergeGroup));
+    const size_t at_oc[2] = {place(H.oc_jobs[0].size() * 4), place(H.oc_jobs[1].size() * 4)};
+    if (!DP.on) {
+        int rc;
+        if ((rc = L.h_plan.reserve(place.bytes + 64)) || (rc = L.d_plan.reserve(place.bytes + 64))) return rc;
+        uint8_t* hp = (uint8_t*)L.h_plan.p;
+        auto put = [&](size_t at, const void* src, size_t bytes) { if (bytes) memcpy(hp + at, src, bytes); };
+        put(at_q, P.q.data(), P.q.size() * sizeof(KwQueryDev)); put(at_w, work.data(), work.size() * sizeof(KwWorkItem));
+        put(at_aux, P.aux.data(), P.aux.size() * 4); put(at_mf, P.mf.data(), P.mf.size() * sizeof(KwQueryMF));
+        for (int tb = 0; tb < 4; tb++) put(at_hoff[tb], H.tp[tb].hoff.data(), H.tp[tb].hoff.size() * 8);
+        put(at_grp, P.groups.data(), P.groups.size() * sizeof(KwMergeGroup));
+        for (int tb = 0; tb < 2; tb++) put(at_oc[tb], H.oc_jobs[tb].data(), H.oc_jobs[tb].size() * 4);
+        TSGPU_HIP_TRY(hipMemcpyAsync(L.d_plan.p, hp, place.bytes, hipMemcpyHostToDevice, s));
+    }
+    const uint8_t* const dplan = (const uint8_t*)L.d_plan.p;
+    T.dq = DP.on ? DP.dq : (const KwQueryDev*)(dplan + at_q); T.dw = DP.on ? DP.dw : (const KwWorkItem*)(dplan + at_w);
+    T.daux = DP.on ? DP.daux : (const uint32_t*)(dplan + at_aux); T.mf = (const KwQueryMF*)(dplan + at_mf);
+    for (int tb = 0; tb < 4; tb++) T.hoff[tb] = DP.on ? DP.hoff + H.first[tb] : (const uint64_t*)(dplan + at_hoff[tb]);
+    T.groups = (const KwMergeGroup*)(dplan + at_grp);
+    for (int tb = 0; tb < 2; tb++) T.oc_jobs[tb] = (const uint32_t*)(dplan + at_oc[tb]);
+    return TSGPU_OK;
+}
+
+// ---- scratch: pw partial lists of k_stride slots (one per work item + one per merge group) ----
+int reserve_partials(KwLane& L, size_t pw, uint32_t KS, KwPartials& part) {
+    int rc;
+    const size_t slots = pw * KS * 8;
+    if ((rc = L.d_part_s0.reserve(slots)) || (rc = L.d_part_s1.reserve(slots)) || (rc = L.d_part_s2.reserve(slots)) || (rc = L.d_part_key.reserve(slots))) return rc;
+    if ((rc = L.d_part_cnt.reserve(pw * 4)) || (rc = L.d_part_nm.reserve(pw * 4)) || (rc = L.d_part_ne.reserve(pw * 4)) || (rc = L.d_part_ow.reserve(pw * 8)) || (rc = L.d_part_f.reserve(pw * 16))) return rc;
+    part.s0 = L.d_part_s0.as<int64_t>(); part.s1 = L.d_part_s1.as<int64_t>(); part.s2 = L.d_part_s2.as<int64_t>();
+    part.key = L.d_part_key.as<int64_t>(); part.cnt = L.d_part_cnt.as<uint32_t>(); part.n_match = L.d_part_nm.as<uint32_t>();
+    part.n_emit = L.d_part_ne.as<uint32_t>(); part.off_words = L.d_part_ow.as<uint64_t>(); part.k_stride = KS;
+    part.n_match1 = L.d_part_f.as<uint32_t>(); part.first_rank = part.n_match1 + pw; part.last_rank = part.first_rank + pw; part.fflags = part.last_rank + pw;
+    return TSGPU_OK;
+}
+KwPartials shifted(KwPartials pb, size_t sh) {             // every kernel indexes the partials by its own blockIdx: shift the bases
+    const size_t KS = pb.k_stride;
+    pb.s0 += sh * KS; pb.s1 += sh * KS; pb.s2 += sh * KS; pb.key += sh * KS;
+    pb.cnt += sh; pb.n_match += sh; pb.n_emit += sh; pb.off_words += sh;
+    pb.n_match1 += sh; pb.first_rank += sh; pb.last_rank += sh; pb.fflags += sh;
+    return pb;
+}
+
+// host outputs: ONE device image [n_hits | num_matched | off_words | keys | scores | text_match | vector_distance | msi]
+// -> one device-to-host copy per batch (seven separate copies cost a small batch ~60 us of launch overhead)
+struct KwResultImage {
+    size_t n_queries, k_stride, n_hits = 0, num_matched, off_words, keys, scores, text_match, vector_distance, msi, bytes;
+    KwResultImage(size_t n, size_t ks) : n_queries(n), k_stride(ks) {
+        const size_t slots = n * ks;
+        num_matched = (n * 4 + 7) & ~(size_t)7; off_words = num_matched + n * 8; keys = off_words + n * 8;
+        scores = keys + slots * 8; text_match = scores + slots * 24; vector_distance = text_match + slots * 8; msi = vector_distance + ((slots * 4 + 7) & ~(size_t)7);
+        bytes = msi + ((slots + 7) & ~(size_t)7);
+    }
+    template <class Arrays>
+    void alias(uint8_t* b, Arrays& h) const {               // h's arrays point INTO the image at b (a tsgpu_hits: alias_out of the coalesced round)
+        h.n_hits = (uint32_t*)(b + n_hits); h.num_matched = (uint64_t*)(b + num_matched);
+        h.keys = (uint64_t*)(b + keys); h.scores = (int64_t*)(b + scores); h.text_match = (int64_t*)(b + text_match);
+        h.vector_distance = (float*)(b + vector_distance); h.match_score_index = (int8_t*)(b + msi);
+    }
+    void bind(uint8_t* b, KwOut& o) const { alias(b, o); o.off_words = (uint64_t*)(b + off_words); }      // the kernels write the image at b
+    void copy_live_rows(const uint8_t* b, const tsgpu_hits& h) const {      // the host image at b into h's arrays (the optional ones may be NULL)
+        const uint32_t* nh = (const uint32_t*)(b + n_hits);
+        memcpy(h.n_hits, nh, n_queries * 4);
+        if (h.num_matched) memcpy(h.num_matched, b + num_matched, n_queries * 8);
+        for (size_t i = 0; i < n_queries; i++) {           // only the hits: slots behind n_hits[i] are undefined in the image too
+            const size_t at = i * k_stride, n = std::min<size_t>(nh[i], k_stride);
+            memcpy(h.keys + at, b + keys + at * 8, n * 8);
+            memcpy(h.scores + at * 3, b + scores + at * 24, n * 24);
+            if (h.text_match) memcpy(h.text_match + at, b + text_match + at * 8, n * 8);
+            if (h.vector_distance) memcpy(h.vector_distance + at, b + vector_distance + at * 4, n * 4);
+            if (h.match_score_index) memcpy(h.match_score_index + at, b + msi + at, n);
+        }
+    }
+};
+
+// ---- launch: the index view of the batch, then find / score (or fused) kernels per table, wildcard scans, merge groups, merge ----
+struct LaunchStats { uint32_t hit_groups = 0; bool find_marked = false; };
+int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap, const Plan& P, const HitTables& H, const KwStaged& T, int cap, uint32_t n_queries,
+                 bool timing, bool count_touched, bool vflat, LaunchStats& st) {
+    int rc;
+    IndexView v = make_view(ctx, snap);
+    v.mf = T.mf;
+    if (P.fbits_words) {
+        if ((rc = L.d_fbits.reserve(P.fbits_words * 4))) return rc;
+        TSGPU_HIP_TRY(hipMemsetAsync(L.d_fbits.p, 0, P.fbits_words * 4, s));
+    }
+    v.fbits = L.d_fbits.as<uint32_t>();
+    if ((rc = L.d_t0.reserve(64))) return rc;
+    v.t0 = L.d_t0.as<long long>(); v.ticks_per_us = ctx->ticks_per_us;
+    if (P.any_deadline) {
+        if ((rc = L.d_cut.reserve((size_t)n_queries * 4))) return rc;
+        TSGPU_HIP_TRY(hipMemsetAsync(L.d_cut.p, 0, (size_t)n_queries * 4, s));
+        hipLaunchKernelGGL(kw_stamp_kernel, dim3(1), dim3(1), 0, s, L.d_t0.as<long long>());       // the queries' budgets count from here
+    }
+    v.cutoff = L.d_cut.as<uint32_t>();
+    if (count_touched) {                         // measurement option: the find kernel's COUNT instantiation adds the bytes it requests here
+        if ((rc = L.d_touched.reserve(8 * 8))) return rc;
+        TSGPU_HIP_TRY(hipMemsetAsync(L.d_touched.p, 0, 8 * 8, s));
+        v.touched = L.d_touched.as<unsigned long long>();
+    }
+    const KwQueryDev* dq = T.dq; const KwWorkItem* dw = T.dw; const uint32_t* daux = T.daux; uint32_t* ids_out = T.ids_out;
+    if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[0], s));
+    auto run_table = [&](int tb, auto tmax_tag, auto mf_tag) {
+        constexpr int TM = decltype(tmax_tag)::value;
+        constexpr bool MFT = decltype(mf_tag)::value;
+        const size_t nws = H.n[tb], first = H.first[tb];
+        const TablePlan& tp = H.tp[tb];
+        if (nws == 0) return;
+        if (tp.two) {
+            st.hit_groups += (uint32_t)tp.group_start.size() - 1;
+            for (size_t gi = 0; gi + 1 < tp.group_start.size(); gi++) {
+                const size_t a = tp.group_start[gi], b = tp.group_start[gi + 1];
+                if (b <= a) continue;
+                if constexpr (MFT) {
+                    MfOrderedCount oc;
+                    if (!H.oc_jobs[tb - 2].empty() && tp.group_start.size() == 2) {
+                        oc.jobs = T.oc_jobs[tb - 2]; oc.n_jobs = (uint32_t)H.oc_jobs[tb - 2].size(); oc.table_first = (uint32_t)first;
+                        oc.work_all = dw; oc.part_all = T.part;
+                    }
+                    const int mf_pipe = !ctx->kw_mf_pipelined ? 0 : (P.mf_max_fields <= 2 ? 2 : (P.mf_max_fields <= 4 ? 4 : 0));
+                    if (mf_pipe) ctx->kw_mf_pipelined_launches++;
+                    launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, oc, !P.any_aux && !P.any_array, mf_pipe);
+                }
+                else {
+                    const bool mark = !st.find_marked;
+                    st.find_marked = true;
+                    launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux);
+                }
+            }
+        } else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out);
+        else with_cap(cap, [&](auto c) { launch_search<TM, decltype(c)::value>(s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_s2); });
+    };
+    run_table(0, std::integral_constant<int, 3>(), std::false_type());
+    run_table(1, std::integral_constant<int, KW_MAX_TOKENS>(), std::false_type());
+    run_table(2, std::integral_constant<int, 3>(), std::true_type());
+    run_table(3, std::integral_constant<int, KW_MAX_TOKENS>(), std::true_type());
+    const size_t sh = H.first[4];
+    if (H.n[4]) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
+    if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[1], s));
+    if (!P.groups.empty()) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_merge_groups_kernel<decltype(c)::value>), dim3((uint32_t)P.groups.size()), dim3(KW_THREADS), 0, s, dq, T.part, T.groups); });
+    with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_merge_kernel<decltype(c)::value>), dim3(n_queries), dim3(KW_THREADS), 0, s, dq, T.part, T.o, ids_out, dw, ctx->kw_merge_select_min); });
+    if (vflat) hipLaunchKernelGGL(kw_vflat_distance_kernel, dim3(n_queries), dim3(KW_THREADS), 0, s, dq, daux, T.o);     // KV::vector_distance of the hits
+    if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[2], s));
+    TSGPU_HIP_TRY(hipGetLastError());
+    return TSGPU_OK;
+}
+
+// ---- results: device output (img == nullptr: the kernels wrote the caller's arrays), or the host image (zero-copy / staged through the lane's
+//      pinned buffer) or direct copies; then status and cut-off flags, with the deadlines the kernels raised ----
+int deliver(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, Plan& P, const KwOut& o, const KwResultImage* img, bool zero_copy, bool alias_out, uint32_t n_queries,
+            tsgpu_hits* out, std::vector<uint64_t>& off_words) {
+    if (img) {
+        // small results: the whole image through the pinned staging buffer (a pageable destination costs ~150 us per copy call);
+        // large ones: straight to the caller's arrays (the runtime pipelines them)
+        if (img->bytes <= (8u << 20)) {
+            if (!zero_copy) {
+                if (int rc = L.h_out.reserve(img->bytes + 64)) return rc;
+                TSGPU_HIP_TRY(hipMemcpyAsync(L.h_out.p, L.d_out_keys.p, img->bytes, hipMemcpyDeviceToHost, s));
+            }
+            // (a spinning wait costs one CPU per lane for the whole round: with many request threads — and a CPU quota — the waiting
+            //  thread sleeps on a blocking event instead: +20-40 us of latency, four CPUs back)
+            if (ctx->kw_callers.load() >= ctx->blocking_sync_min_callers) TSGPU_HIP_TRY(sleeping_wait(L, s));
+            else TSGPU_HIP_TRY(hipStreamSynchronize(s));
+            uint8_t* hb = (uint8_t*)L.h_out.p;
+            memcpy(off_words.data(), hb + img->off_words, (size_t)n_queries * 8);
+            if (alias_out) img->alias(hb, *out); else img->copy_live_rows(hb, *out);
+        } else {
+            const size_t slots = (size_t)n_queries * o.k_stride;
+            TSGPU_HIP_TRY(hipMemcpyAsync(out->n_hits, o.n_hits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, s));
+            if (out->num_matched) TSGPU_HIP_TRY(hipMemcpyAsync(out->num_matched, o.num_matched, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(out->keys, o.keys, slots * 8, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(out->scores, o.scores, slots * 24, hipMemcpyDeviceToHost, s));
+            if (out->text_match) TSGPU_HIP_TRY(hipMemcpyAsync(out->text_match, o.text_match, slots * 8, hipMemcpyDeviceToHost, s));
+            if (out->vector_distance) TSGPU_HIP_TRY(hipMemcpyAsync(out->vector_distance, o.vector_distance, slots * 4, hipMemcpyDeviceToHost, s));
+            if (out->match_score_index) TSGPU_HIP_TRY(hipMemcpyAsync(out->match_score_index, o.match_score_index, slots, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(off_words.data(), o.off_words, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        }
+        for (uint32_t i = 0; i < n_queries; i++) out->status[i] = P.status[i];
+        if (out->search_cutoff) for (uint32_t i = 0; i < n_queries; i++) out->search_cutoff[i] = P.cutoff[i];
+    } else {
+        TSGPU_HIP_TRY(hipMemcpyAsync(out->status, P.status.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, s));
+        if (out->search_cutoff) TSGPU_HIP_TRY(hipMemcpyAsync(out->search_cutoff, P.cutoff.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, s));
+        TSGPU_HIP_TRY(hipMemcpyAsync(off_words.data(), o.off_words, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (P.any_deadline) {                        // work items that ran out of time raised their query's flag: partial hits + search_cutoff
+        std::vector<uint32_t> cut(n_queries);
+        TSGPU_HIP_TRY(hipMemcpy(cut.data(), L.d_cut.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
+        bool any = false;
+        for (uint32_t i = 0; i < n_queries; i++) if (cut[i]) { P.cutoff[i] = 1; any = true; }
+        if (any && out->search_cutoff) {
+            if (!img) TSGPU_HIP_TRY(hipMemcpy(out->search_cutoff, P.cutoff.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice));
+            else for (uint32_t i = 0; i < n_queries; i++) out->search_cutoff[i] = P.cutoff[i];
+        }
+    }
+    return TSGPU_OK;
+}
+
+// sort keys of query i that read a column value per match (the device planner leaves P.q on the device: the caller's query tells)
+uint32_t n_column_sort_keys(const Plan& P, bool dev_plan, const tsgpu_kw_query* queries, uint32_t i) {
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < (dev_plan ? queries[i].n_sort : P.q[i].n_sort); k++) n += sort_kind_reads_key(dev_plan ? queries[i].sort[k].kind : P.q[i].sort_kind[k]) ? 1 : 0;
+    return n;
+}
+
+// ---- bookkeeping: timings + algorithmic bytes; num_matched = the host's counts (nullptr: device output, or not asked for) ----
+void record_timings(tsgpu_ctx* ctx, KwLane& L, bool timing, const LaunchStats& st, uint64_t hit_records, const Plan& P, bool dev_plan, const tsgpu_kw_query* queries,
+                    const std::vector<uint64_t>& off_words, const uint64_t* num_matched) {
+    float ms_a = 0, ms_b = 0, ms_find = 0;
+    if (timing) { (void)hipEventElapsedTime(&ms_a, L.ev[0], L.ev[1]); (void)hipEventElapsedTime(&ms_b, L.ev[1], L.ev[2]); }
+    if (timing && st.find_marked && st.hit_groups == 1) (void)hipEventElapsedTime(&ms_find, L.ev[0], L.ev[3]);       // one find launch, then one score launch
+    uint64_t bytes = P.list_bytes;
+    for (uint32_t i = 0; i < off_words.size(); i++) bytes += 4ull * off_words[i] + (num_matched ? 8ull * num_matched[i] * n_column_sort_keys(P, dev_plan, queries, i) : 0);
+    std::lock_guard<std::mutex> tl(ctx->tm_mu);
+    ctx->timings.kw_search_ms = ms_a; ctx->timings.kw_merge_ms = ms_b; ctx->timings.kw_find_ms = ms_find; ctx->timings.total_ms = ms_a + ms_b;
+    ctx->timings.kw_algorithmic_bytes = bytes;
+    ctx->kw_last_hit_groups = st.hit_groups; ctx->kw_last_hit_records = hit_records;
+}
+
+// measurement option kw_count_touched: the bytes the find kernel counted + the score kernel's, computed from the counts of matches
+int record_touched(tsgpu_ctx* ctx, KwLane& L, const Plan& P, bool dev_plan, const tsgpu_kw_query* queries, uint32_t n_queries, const uint64_t* nm, const uint64_t* nm_dev) {
+    uint64_t c[8];
+    TSGPU_HIP_TRY(hipMemcpy(c, L.d_touched.p, sizeof(c), hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> tl(ctx->tm_mu);
+    tsgpu_kw_touched& tt = ctx->kw_touched;
+    tt.find_driver_ids = c[0]; tt.find_metadata = c[1]; tt.find_tile_dma = c[2]; tt.find_probes = c[3]; tt.find_records = c[4];
+    tt.find_work_items = c[5]; tt.find_hit_records = c[6];
+    tt.find_requested_bytes = c[0] + c[1] + c[2] + c[3] + c[4];
+    // the score kernel's requests per hit record are fixed sizes (kw_score_kernel / load_runs_staged): the record itself, per token one
+    // BlockMeta (32 B), the offset_index pair (two 8-byte fetches) and the first offsets (8 B); per numeric sort key one column value; the
+    // rare third.. occurrence of a token in a document (one more 8-byte fetch each) is not counted
+    uint64_t sb = 0;
+    std::vector<uint64_t> nm_host;
+    if (nm_dev) {                                            // (measurement only: one small read-back)
+        nm_host.resize(n_queries);
+        if (hipMemcpy(nm_host.data(), nm_dev, (size_t)n_queries * 8, hipMemcpyDeviceToHost) == hipSuccess) nm = nm_host.data();
+    }
+    for (uint32_t i = 0; nm && !dev_plan && i < n_queries; i++)
+        sb += nm[i] * (4ull * ((P.q[i].n_lists <= 3 ? 3 : KW_MAX_TOKENS) + 1) + 56ull * P.q[i].n_lists + 8ull * n_column_sort_keys(P, dev_plan, queries, i));
+    tt.score_requested_bytes = sb;
+    return TSGPU_OK;
+}
+
+// ---- matched ids (id_buff / all_result_ids, src/index.cpp:5549, 5565): every work item left an ascending segment ----
+// legacy single-caller API (tsgpu_result_ids): remember where the segments live (ne: the work items' emitted counts; empty = no ids kept)
+void record_last_ids(KwLane& L, const Plan& P, const std::vector<KwWorkItem>& work, const std::vector<uint32_t>& ne, uint32_t n_queries) {
+    L.last_ids_off.assign(n_queries, 0); L.last_ids_unsorted.assign(n_queries, 0);
+    L.last_chunk_emit.assign(n_queries, {}); L.last_chunk_off.assign(n_queries, {});
+    for (uint32_t i = 0; !ne.empty() && i < n_queries; i++) {
+        if (P.status[i] != TSGPU_OK || P.q[i].n_work == 0) continue;
+        L.last_ids_off[i] = P.q[i].ids_out_off;
+        L.last_chunk_emit[i].assign(ne.begin() + P.q[i].first_work, ne.begin() + P.q[i].first_work + P.q[i].n_work);
+        L.last_chunk_off[i].resize(P.q[i].n_work);
+        for (uint32_t c = 0; c < P.q[i].n_work; c++) L.last_chunk_off[i][c] = work[P.q[i].first_work + c].ids_out_off;
+        L.last_ids_unsorted[i] = P.q[i].mf_index != KW_NONE;      // several driver lists: segments are sorted, their union is not
+    }
+}
+// per-call id lists: the segments are gathered into one dense array on the device (one launch, one download) and belong
+// to THIS call — concurrent callers never see each other's ids
+int build_id_lists(KwLane& L, hipStream_t s, const Plan& P, const std::vector<KwWorkItem>& work, const std::vector<uint32_t>& ne, const uint32_t* ids_out, uint32_t n_queries,
+                   tsgpu_id_lists& il, DevBuf* ids_dev, bool* ids_dev_done) {
+    il.begin.assign((size_t)n_queries + 1, 0);
+    std::vector<KwIdCopy> segs;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_queries; i++) {
+        il.begin[i] = at;
+        if (P.status[i] != TSGPU_OK || P.q[i].n_work == 0) continue;
+        for (uint32_t c = 0; c < P.q[i].n_work; c++) {
+            const uint32_t cnt = ne[P.q[i].first_work + c];
+            if (!cnt) continue;
+            segs.push_back({P.q[i].ids_out_off + work[P.q[i].first_work + c].ids_out_off, at, cnt, 0u});
+            at += cnt;
+        }
+    }
+    il.begin[n_queries] = at;
+    bool to_dev = ids_dev != nullptr;                 // the ids stay on the device, in the caller's buffer (several driver lists: the union is sorted on the host below)
+    for (uint32_t i = 0; to_dev && i < n_queries; i++) if (P.status[i] == TSGPU_OK && P.q[i].mf_index != KW_NONE) to_dev = false;
+    if (ids_dev_done) *ids_dev_done = to_dev;
+    il.ids.resize(to_dev ? 0 : at);                   // (on the device: nothing to download)
+    if (!at) return TSGPU_OK;
+    DevBuf& dst = to_dev ? *ids_dev : L.d_idflat;
+    int rc;
+    if ((rc = dst.reserve(at * 4)) || (rc = upload(L.d_idseg, segs.data(), segs.size() * sizeof(KwIdCopy), s))) return rc;
+    hipLaunchKernelGGL(kw_ids_gather_kernel, dim3((uint32_t)segs.size()), dim3(KW_THREADS), 0, s, ids_out, L.d_idseg.as<KwIdCopy>(), dst.as<uint32_t>());
+    TSGPU_HIP_TRY(hipGetLastError());
+    if (!to_dev) TSGPU_HIP_TRY(hipMemcpyAsync(il.ids.data(), dst.p, at * 4, hipMemcpyDeviceToHost, s));
+    TSGPU_HIP_TRY(hipStreamSynchronize(s));           // (on the device: the consumer runs on another stream)
+    for (uint32_t i = 0; !to_dev && i < n_queries; i++)                      // several driver lists (query_by over several fields): ascending union
+        if (P.q[i].mf_index != KW_NONE && P.status[i] == TSGPU_OK) std::sort(il.ids.begin() + il.begin[i], il.ids.begin() + il.begin[i + 1]);
+    return TSGPU_OK;
+}
+}  // namespace
+
+extern "C" {
 // the lane's mutex is held by the caller
 static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* queries, uint32_t n_queries, tsgpu_hits* out, const BatchOpts& bo) {
     (void)hipSetDevice(ctx->device);
     const std::shared_ptr<const Snapshot> snap_ref = ctx->snapshot();     // this batch runs on this snapshot, whatever is committed meanwhile
     const Snapshot& snap = *snap_ref;
-    const bool wildcard = bo.wildcard;
     const bool keep_ids = bo.keep_ids || bo.id_lists != nullptr;
-    std::vector<int32_t>* status_host = bo.status_host;
     hipStream_t s = L.stream;
     SliceChain::Turn chain_turn(bo.chain, bo.chain_index);     // (passes the turn on when this slice leaves, whatever happens to it)
     try {
         static const bool host_timing = getenv("TSGPU_HOST_TIMING") != nullptr;      // diagnostics: host phases of the call on stderr
         const uint64_t t_enter = now_us();
-        Plan P;
-        DevPlan DP;
+        Plan P; DevPlan DP;
         int rc;
-        // big batches of plain single-field queries: the plan is made on the device (three small kernels, one read-back) instead of ~0.5 ms of
-        // host threads; any other shape — and anything the device planner hands back — goes through plan_batch()
-        // (not for the chained slices of a sliced host delivery: there the host plans slice i + 1 WHILE slice i runs, and a planning kernel on the
-        //  second lane would wait behind the running find kernel for a place on the chip — measured: 10.05 -> 10.18 ms per 10 000 queries)
-        // (batches that keep the matched ids: only when nobody reads the segments back per query — the candidate call marks its id sets from the device tables)
-        if (!wildcard && !bo.present_elsewhere && (!keep_ids || (!bo.record_last && !bo.id_lists)) && !bo.vflat && (!bo.chain || (bo.chain_index == 0 && ctx->kw_host_split_device_plan)) && ctx->kw_two_kernels && ctx->kw_device_plan_min_queries && n_queries >= ctx->kw_device_plan_min_queries) {
+        if (device_plan_applies(ctx, bo, keep_ids, n_queries)) {
             if ((rc = plan_batch_device(ctx, L, snap, queries, n_queries, P, DP, s))) return rc;
             if (DP.on) ctx->kw_device_plans.fetch_add(1); else ctx->kw_device_plan_fallbacks.fetch_add(1);
             if (DP.on && keep_ids) P.ids_total = (DP.hit_blocks[0] + DP.hit_blocks[1]) * (uint64_t)BLOCK_IDS;
         }
-        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, wildcard, bo.vflat, bo.present_elsewhere))) return rc;
+        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, bo.wildcard, bo.vflat, bo.present_elsewhere))) return rc;
         const uint64_t t_planned = now_us();
         if (out->k_stride < P.max_k) return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_search_batch: k_stride smaller than the largest topster_size");
-        const uint32_t n_work = DP.on ? DP.n_work[0] + DP.n_work[1]
-                                      : (uint32_t)(P.work_small.size() + P.work_big.size() + P.work_mf_small.size() + P.work_mf_big.size() + P.work_wild.size());
         const uint32_t KS = out->k_stride;
         const int cap = P.max_k + KW_THREADS <= 512 ? 512 : (P.max_k + KW_THREADS <= 1024 ? 1024 : 2048);
 
-        // ---- the plan travels in ONE pinned staging buffer and ONE host-to-device copy (queries, work items, aux ids, multi-field
-        //      descriptors, hit-record offsets): a pageable source costs a staged synchronous copy per call, five calls per batch ----
+        // ---- staging: hit-buffer groups, the plan image, scratch, the outputs ----
         std::vector<KwWorkItem> work(P.work_small);
         work.insert(work.end(), P.work_big.begin(), P.work_big.end());
         work.insert(work.end(), P.work_mf_small.begin(), P.work_mf_small.end());
         work.insert(work.end(), P.work_mf_big.begin(), P.work_mf_big.end());
         work.insert(work.end(), P.work_wild.begin(), P.work_wild.end());
         P.aux.push_back(0);
-        // single-field tables (<= 3 tokens / up to 10 tokens) and multi-field tables: find + score kernels when the hit buffer fits, else the
-        // fused kernel. A work item can yield at most one hit per driver id, so its segment of the hit buffer holds (blk_end - blk_begin) * 256
-        // records of 1 + TMAX words; the items run in groups whose segments fit the budget.
-        struct TablePlan { bool two = false; std::vector<uint64_t> hoff; std::vector<size_t> group_start; uint64_t need = 0; size_t rec_bytes = 0; size_t hoff_at = 0; };
-        uint64_t hit_records = 0;
-        auto prep_table = [&](const std::vector<KwWorkItem>& tab, int TM, bool MFT) {
-            TablePlan tp;
-            tp.group_start.assign(1, 0);
-            if (tab.empty()) return tp;
-            const size_t nws = tab.size();
-            tp.rec_bytes = (size_t)((MFT ? TM * KW_MAX_FIELDS : TM) + 1) * 4;
-            tp.two = ctx->kw_two_kernels;
-            if (tp.two) {
-                uint64_t largest = 0, all = 0;
-                for (size_t i = 0; i < nws; i++) { const uint64_t c = (uint64_t)(tab[i].blk_end - tab[i].blk_begin) * BLOCK_IDS; largest = std::max(largest, c); all += c; }
-                hit_records += all;
-                const uint64_t budget = std::max<uint64_t>(ctx->kw_hit_buffer_records ? ctx->kw_hit_buffer_records : ((uint64_t)ctx->kw_hit_buffer_mb << 20) / tp.rec_bytes, largest);
-                tp.hoff.resize(nws);
-                uint64_t used = 0;
-                for (size_t i = 0; i < nws; i++) {
-                    const uint64_t c = (uint64_t)(tab[i].blk_end - tab[i].blk_begin) * BLOCK_IDS;
-                    if (used + c > budget) { tp.group_start.push_back(i); used = 0; }
-                    tp.hoff[i] = used; used += c; tp.need = std::max(tp.need, used);
-                }
-                tp.group_start.push_back(nws);
-                tp.two = tp.group_start.size() <= 3;          // each group drains the chip between its two kernels: beyond two groups the fused kernel wins
-            }
-            if (tp.two && L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * tp.rec_bytes)) {
-                (void)hipGetLastError();                // no room for the hit buffer: the fused kernel needs none
-                tp.two = false;
-            }
-            if (!tp.two) tp.hoff.clear();
-            return tp;
-        };
-        TablePlan tps[4] = {prep_table(P.work_small, 3, false), prep_table(P.work_big, KW_MAX_TOKENS, false), prep_table(P.work_mf_small, 3, true),
-                            prep_table(P.work_mf_big, KW_MAX_TOKENS, true)};
-        size_t tab_n[5] = {P.work_small.size(), P.work_big.size(), P.work_mf_small.size(), P.work_mf_big.size(), P.work_wild.size()};
-        if (DP.on) {                                    // the device planner's two tables: one group each (it checked the budget), offsets already on the device
-            for (int tb = 0; tb < 2; tb++) {
-                TablePlan& tp = tps[tb];
-                tab_n[tb] = DP.n_work[tb];
-                if (!DP.n_work[tb]) continue;
-                tp.two = true;
-                tp.rec_bytes = (size_t)((tb == 0 ? 3 : KW_MAX_TOKENS) + 1) * 4;
-                tp.need = DP.hit_blocks[tb] * (uint64_t)BLOCK_IDS;
-                tp.group_start = {0, (size_t)DP.n_work[tb]};
-                hit_records += tp.need;
-                if ((rc = L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * tp.rec_bytes))) return rc;
-            }
-        }
-        // multi-field queries with filter + excluded ids: counted from the hit records of ONE find launch of their table; a table that was
-        // cut into groups or runs fused cannot serve them -> 501 for those queries (their hits are not reported)
-        std::vector<uint32_t> oc_jobs[2];
-        for (uint32_t qi : P.ordered_count_q) {
-            const int tb = P.q[qi].n_lists <= 3 ? 0 : 1;
-            const TablePlan& tp = tps[2 + tb];
-            if (tp.two && tp.group_start.size() == 2) oc_jobs[tb].push_back(qi);
-            else if (P.status[qi] == TSGPU_OK) P.status[qi] = TSGPU_ERR_UNSUPPORTED;
-        }
-        size_t plan_bytes = 0;
-        auto place = [&](size_t bytes) { const size_t at = (plan_bytes + 63) & ~(size_t)63; plan_bytes = at + bytes; return at; };
-        const size_t at_q = place(P.q.size() * sizeof(KwQueryDev)), at_w = place(work.size() * sizeof(KwWorkItem)), at_aux = place(P.aux.size() * 4),
-                     at_mf = place(P.mf.size() * sizeof(KwQueryMF));
-        for (auto& tp : tps) tp.hoff_at = place(tp.hoff.size() * 8);
-        const size_t at_grp = place(P.groups.size() * sizeof(KwMergeGroup));
-        const size_t at_oc[2] = {place(oc_jobs[0].size() * 4), place(oc_jobs[1].size() * 4)};
-        if (!DP.on && ((rc = L.h_plan.reserve(plan_bytes + 64)) || (rc = L.d_plan.reserve(plan_bytes + 64)))) return rc;
-        if (!DP.on) {
-            uint8_t* hp = (uint8_t*)L.h_plan.p;
-            memcpy(hp + at_q, P.q.data(), P.q.size() * sizeof(KwQueryDev));
-            memcpy(hp + at_w, work.data(), work.size() * sizeof(KwWorkItem));
-            memcpy(hp + at_aux, P.aux.data(), P.aux.size() * 4);
-            if (!P.mf.empty()) memcpy(hp + at_mf, P.mf.data(), P.mf.size() * sizeof(KwQueryMF));
-            for (auto& tp : tps) if (!tp.hoff.empty()) memcpy(hp + tp.hoff_at, tp.hoff.data(), tp.hoff.size() * 8);
-            if (!P.groups.empty()) memcpy(hp + at_grp, P.groups.data(), P.groups.size() * sizeof(KwMergeGroup));
-            for (int tb = 0; tb < 2; tb++) if (!oc_jobs[tb].empty()) memcpy(hp + at_oc[tb], oc_jobs[tb].data(), oc_jobs[tb].size() * 4);
-            TSGPU_HIP_TRY(hipMemcpyAsync(L.d_plan.p, hp, plan_bytes, hipMemcpyHostToDevice, s));
-        }
-        uint8_t* const dplan = (uint8_t*)L.d_plan.p;
-
-        // ---- scratch ----
-        const size_t pw = (size_t)std::max<uint32_t>(n_work, 1) + P.groups.size();      // partial lists: one per work item + one per merge group
-        if ((rc = L.d_part_s0.reserve(pw * KS * 8))) return rc;
-        if ((rc = L.d_part_s1.reserve(pw * KS * 8))) return rc;
-        if ((rc = L.d_part_s2.reserve(pw * KS * 8))) return rc;
-        if ((rc = L.d_part_key.reserve(pw * KS * 8))) return rc;
-        if ((rc = L.d_part_cnt.reserve(pw * 4))) return rc;
-        if ((rc = L.d_part_nm.reserve(pw * 4))) return rc;
-        if ((rc = L.d_part_ne.reserve(pw * 4))) return rc;
-        if ((rc = L.d_part_ow.reserve(pw * 8))) return rc;
-        if ((rc = L.d_part_f.reserve(pw * 16))) return rc;
-        if ((rc = L.d_out_ow.reserve((size_t)n_queries * 8))) return rc;
-        uint32_t* ids_out = nullptr;
+        HitTables H;
+        if ((rc = plan_hit_tables(ctx, L, P, DP, H))) return rc;
+        const uint32_t n_work = (uint32_t)H.first[5];
+        KwStaged T;
+        if ((rc = upload_plan_image(L, s, P, DP, work, H, T))) return rc;
+        L.last_tab_q = T.dq; L.last_tab_w = T.dw; L.last_tab_n_work = n_work;
+        if ((rc = reserve_partials(L, (size_t)std::max<uint32_t>(n_work, 1) + P.groups.size(), KS, T.part))) return rc;
         if (keep_ids) {
             if ((rc = L.d_ids_out.reserve(std::max<uint64_t>(P.ids_total, 1) * 4))) return rc;
-            ids_out = L.d_ids_out.as<uint32_t>();
+            T.ids_out = L.d_ids_out.as<uint32_t>();
         }
-        KwPartials part;
-        part.s0 = L.d_part_s0.as<int64_t>(); part.s1 = L.d_part_s1.as<int64_t>(); part.s2 = L.d_part_s2.as<int64_t>();
-        part.key = L.d_part_key.as<int64_t>(); part.cnt = L.d_part_cnt.as<uint32_t>(); part.n_match = L.d_part_nm.as<uint32_t>();
-        part.n_emit = L.d_part_ne.as<uint32_t>(); part.off_words = L.d_part_ow.as<uint64_t>(); part.k_stride = KS;
-        part.n_match1 = L.d_part_f.as<uint32_t>(); part.first_rank = part.n_match1 + pw; part.last_rank = part.first_rank + pw; part.fflags = part.last_rank + pw;
-
-        const size_t slots = (size_t)n_queries * KS;
-        KwOut o;
-        o.k_stride = KS;
-        o.off_words = L.d_out_ow.as<uint64_t>();
-        size_t out_at[8] = {0, 0, 0, 0, 0, 0, 0, 0}, out_bytes = 0;
+        T.o.k_stride = KS;
+        const KwResultImage img(n_queries, KS);
         const bool dev_out = out->mem == TSGPU_MEM_DEVICE;
-        bool zero_copy = false;
+        // a SMALL round's merge kernel writes the image straight into the lane's pinned host buffer (device-visible, coherent): no
+        // device-to-host copy kernel (4-25 us) and no launch gap (~6 us) behind the merge; only the hits themselves cross the link
+        const bool zero_copy = !dev_out && img.bytes <= (8u << 20) && n_queries <= ctx->kw_zero_copy_max_queries;
         if (dev_out) {
             if (!out->text_match || !out->vector_distance || !out->match_score_index || !out->num_matched)
                 return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_search_batch: device output needs every tsgpu_hits array");
-            o.keys = out->keys; o.scores = out->scores; o.text_match = out->text_match; o.vector_distance = out->vector_distance;
-            o.match_score_index = out->match_score_index; o.n_hits = out->n_hits; o.num_matched = out->num_matched;
+            if ((rc = L.d_out_ow.reserve((size_t)n_queries * 8))) return rc;
+            T.o.keys = out->keys; T.o.scores = out->scores; T.o.text_match = out->text_match; T.o.vector_distance = out->vector_distance;
+            T.o.match_score_index = out->match_score_index; T.o.n_hits = out->n_hits; T.o.num_matched = out->num_matched; T.o.off_words = L.d_out_ow.as<uint64_t>();
         } else {
-            // host outputs: ONE device image [n_hits | num_matched | off_words | keys | scores | text_match | vector_distance | msi]
-            // -> one device-to-host copy per batch (seven separate copies cost a small batch ~60 us of launch overhead)
-            const size_t nq8 = ((size_t)n_queries * 4 + 7) & ~(size_t)7;
-            out_at[0] = 0; out_at[1] = nq8; out_at[2] = out_at[1] + (size_t)n_queries * 8; out_at[3] = out_at[2] + (size_t)n_queries * 8;
-            out_at[4] = out_at[3] + slots * 8; out_at[5] = out_at[4] + slots * 24; out_at[6] = out_at[5] + slots * 8; out_at[7] = out_at[6] + ((slots * 4 + 7) & ~(size_t)7);
-            out_bytes = out_at[7] + ((slots + 7) & ~(size_t)7);
-            // a SMALL round's merge kernel writes the image straight into the lane's pinned host buffer (device-visible, coherent): no
-            // device-to-host copy kernel (4-25 us) and no launch gap (~6 us) behind the merge; only the hits themselves cross the link
-            zero_copy = out_bytes <= (8u << 20) && n_queries <= ctx->kw_zero_copy_max_queries;
-            if (zero_copy) { if ((rc = L.h_out.reserve(out_bytes + 64))) return rc; }
-            else if ((rc = L.d_out_keys.reserve(out_bytes))) return rc;
-            uint8_t* ob = zero_copy ? (uint8_t*)L.h_out.p : (uint8_t*)L.d_out_keys.p;
-            o.n_hits = (uint32_t*)(ob + out_at[0]); o.num_matched = (uint64_t*)(ob + out_at[1]); o.off_words = (uint64_t*)(ob + out_at[2]);
-            o.keys = (uint64_t*)(ob + out_at[3]); o.scores = (int64_t*)(ob + out_at[4]); o.text_match = (int64_t*)(ob + out_at[5]);
-            o.vector_distance = (float*)(ob + out_at[6]); o.match_score_index = (int8_t*)(ob + out_at[7]);
+            if (zero_copy) { if ((rc = L.h_out.reserve(img.bytes + 64))) return rc; }
+            else if ((rc = L.d_out_keys.reserve(img.bytes))) return rc;
+            img.bind(zero_copy ? (uint8_t*)L.h_out.p : (uint8_t*)L.d_out_keys.p, T.o);
         }
 
         // ---- launch ----
@@ -1534,284 +1787,31 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
             if (bo.chain->last) TSGPU_HIP_TRY(hipStreamWaitEvent(s, bo.chain->last, 0));
         }
         const uint64_t t_uploaded = now_us();
-        IndexView v = make_view(ctx, snap);
-        v.mf = (const KwQueryMF*)(dplan + at_mf);
-        if (P.fbits_words) {
-            if ((rc = L.d_fbits.reserve(P.fbits_words * 4))) return rc;
-            TSGPU_HIP_TRY(hipMemsetAsync(L.d_fbits.p, 0, P.fbits_words * 4, s));
-        }
-        v.fbits = L.d_fbits.as<uint32_t>();
-        if ((rc = L.d_t0.reserve(64))) return rc;
-        v.t0 = L.d_t0.as<long long>();
-        v.ticks_per_us = ctx->ticks_per_us;
-        if (P.any_deadline) {
-            if ((rc = L.d_cut.reserve((size_t)n_queries * 4))) return rc;
-            TSGPU_HIP_TRY(hipMemsetAsync(L.d_cut.p, 0, (size_t)n_queries * 4, s));
-            hipLaunchKernelGGL(kw_stamp_kernel, dim3(1), dim3(1), 0, s, L.d_t0.as<long long>());       // the queries' budgets count from here
-        }
-        v.cutoff = L.d_cut.as<uint32_t>();
-        const bool count_touched = ctx->kw_count_touched;
-        if (count_touched) {                         // measurement option: the find kernel's COUNT instantiation adds the bytes it requests here
-            if ((rc = L.d_touched.reserve(8 * 8))) return rc;
-            TSGPU_HIP_TRY(hipMemsetAsync(L.d_touched.p, 0, 8 * 8, s));
-            v.touched = L.d_touched.as<unsigned long long>();
-        }
-        const KwQueryDev* dq = DP.on ? DP.dq : (const KwQueryDev*)(dplan + at_q);
-        const KwWorkItem* dw = DP.on ? DP.dw : (const KwWorkItem*)(dplan + at_w);
-        L.last_tab_q = dq; L.last_tab_w = dw; L.last_tab_n_work = n_work;
-        const uint32_t* daux = DP.on ? DP.daux : (const uint32_t*)(dplan + at_aux);
         const bool timing = bo.timing && n_queries >= ctx->kw_timing_min_queries;      // (each record is a marker packet in the stream: ~2 us of a small round)
-        if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[0], s));
-        auto shifted = [&](size_t sh) {                 // every kernel indexes the partials by its own blockIdx: shift the bases
-            KwPartials pb = part;
-            pb.s0 += sh * KS; pb.s1 += sh * KS; pb.s2 += sh * KS; pb.key += sh * KS;
-            pb.cnt += sh; pb.n_match += sh; pb.n_emit += sh; pb.off_words += sh;
-            pb.n_match1 += sh; pb.first_rank += sh; pb.last_rank += sh; pb.fflags += sh;
-            return pb;
-        };
-        uint32_t hit_groups = 0;
-        bool find_marked = false;
-        auto run_table = [&](size_t nws, const TablePlan& tp, size_t first, auto tmax_tag, auto mf_tag) {
-            constexpr int TM = decltype(tmax_tag)::value;
-            constexpr bool MFT = decltype(mf_tag)::value;
-            if (nws == 0) return;
-            if (tp.two) {
-                hit_groups += (uint32_t)tp.group_start.size() - 1;
-                const uint64_t* hoff_dev = DP.on ? DP.hoff + first : (const uint64_t*)(dplan + tp.hoff_at);
-                for (size_t gi = 0; gi + 1 < tp.group_start.size(); gi++) {
-                    const size_t a = tp.group_start[gi], b = tp.group_start[gi + 1];
-                    if (b <= a) continue;
-                    if constexpr (MFT) {
-                        MfOrderedCount oc;
-                        const int tb = TM == 3 ? 0 : 1;
-                        if (!oc_jobs[tb].empty() && tp.group_start.size() == 2) {
-                            oc.jobs = (const uint32_t*)(dplan + at_oc[tb]); oc.n_jobs = (uint32_t)oc_jobs[tb].size(); oc.table_first = (uint32_t)first;
-                            oc.work_all = dw; oc.part_all = part;
-                        }
-                        const int mf_pipe = !ctx->kw_mf_pipelined ? 0 : (P.mf_max_fields <= 2 ? 2 : (P.mf_max_fields <= 4 ? 4 : 0));
-                        if (mf_pipe) ctx->kw_mf_pipelined_launches++;
-                        launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(first + a), daux, ids_out, L.d_hits.as<uint32_t>(), hoff_dev + a, oc, !P.any_aux && !P.any_array, mf_pipe);
-                    }
-                    else {
-                        const bool mark = !find_marked;
-                        find_marked = true;
-                        launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), hoff_dev + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux);
-                    }
-                }
-            } else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(first), daux, ids_out);
-            else launch_search_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(first), daux, ids_out, P.any_s2);
-        };
-        run_table(tab_n[0], tps[0], 0, std::integral_constant<int, 3>(), std::false_type());
-        size_t sh = tab_n[0];
-        run_table(tab_n[1], tps[1], sh, std::integral_constant<int, KW_MAX_TOKENS>(), std::false_type());
-        sh += tab_n[1];
-        run_table(tab_n[2], tps[2], sh, std::integral_constant<int, 3>(), std::true_type());
-        sh += tab_n[2];
-        run_table(tab_n[3], tps[3], sh, std::integral_constant<int, KW_MAX_TOKENS>(), std::true_type());
-        sh += tab_n[3];
-        if (!P.work_wild.empty()) {
-            const uint32_t nw = (uint32_t)P.work_wild.size();
-            if (cap == 512) hipLaunchKernelGGL((kw_wildcard_kernel<512>), dim3(nw), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(sh), daux, ids_out);
-            else if (cap == 1024) hipLaunchKernelGGL((kw_wildcard_kernel<1024>), dim3(nw), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(sh), daux, ids_out);
-            else hipLaunchKernelGGL((kw_wildcard_kernel<2048>), dim3(nw), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(sh), daux, ids_out);
-        }
-        if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[1], s));
-        if (!P.groups.empty()) {
-            const KwMergeGroup* dg = (const KwMergeGroup*)(dplan + at_grp);
-            const uint32_t ng = (uint32_t)P.groups.size();
-            if (cap == 512) hipLaunchKernelGGL((kw_merge_groups_kernel<512>), dim3(ng), dim3(KW_THREADS), 0, s, dq, part, dg);
-            else if (cap == 1024) hipLaunchKernelGGL((kw_merge_groups_kernel<1024>), dim3(ng), dim3(KW_THREADS), 0, s, dq, part, dg);
-            else hipLaunchKernelGGL((kw_merge_groups_kernel<2048>), dim3(ng), dim3(KW_THREADS), 0, s, dq, part, dg);
-        }
-        launch_merge(cap, s, n_queries, dq, part, o, ids_out, dw, ctx->kw_merge_select_min);
-        if (bo.vflat) hipLaunchKernelGGL(kw_vflat_distance_kernel, dim3(n_queries), dim3(KW_THREADS), 0, s, dq, daux, o);     // KV::vector_distance of the hits
-        if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[2], s));
-        TSGPU_HIP_TRY(hipGetLastError());
+        const bool count_touched = ctx->kw_count_touched;
+        LaunchStats st;
+        if ((rc = launch_batch(ctx, L, s, snap, P, H, T, cap, n_queries, timing, count_touched, bo.vflat != nullptr, st))) return rc;
         if (bo.chain) { TSGPU_HIP_TRY(hipEventRecord(L.ev_chain, s)); bo.chain->last = L.ev_chain; SliceChain* cc = bo.chain; chain_turn.pass(); cc->cv.notify_all(); }
         const uint64_t t_launched = now_us();
 
         // ---- results ----
         std::vector<uint64_t> off_words(n_queries);
-        if (!dev_out) {
-            // small results: the whole image through the pinned staging buffer (a pageable destination costs ~150 us per copy call);
-            // large ones: straight to the caller's arrays (the runtime pipelines them)
-            const bool stage = out_bytes <= (8u << 20);
-            if (stage) {
-                if (!zero_copy) {
-                    if ((rc = L.h_out.reserve(out_bytes + 64))) return rc;
-                    TSGPU_HIP_TRY(hipMemcpyAsync(L.h_out.p, L.d_out_keys.p, out_bytes, hipMemcpyDeviceToHost, s));
-                }
-                // (a spinning wait costs one CPU per lane for the whole round: with many request threads — and a CPU quota — the waiting
-                //  thread sleeps on a blocking event instead: +20-40 us of latency, four CPUs back)
-                if (ctx->kw_callers.load() >= ctx->blocking_sync_min_callers) TSGPU_HIP_TRY(sleeping_wait(L, s));
-                else TSGPU_HIP_TRY(hipStreamSynchronize(s));
-                uint8_t* hb = (uint8_t*)L.h_out.p;
-                const uint32_t* nh = (const uint32_t*)(hb + out_at[0]);
-                memcpy(off_words.data(), hb + out_at[2], (size_t)n_queries * 8);
-                if (bo.alias_out) {
-                    out->n_hits = (uint32_t*)(hb + out_at[0]); out->num_matched = (uint64_t*)(hb + out_at[1]);
-                    out->keys = (uint64_t*)(hb + out_at[3]); out->scores = (int64_t*)(hb + out_at[4]); out->text_match = (int64_t*)(hb + out_at[5]);
-                    out->vector_distance = (float*)(hb + out_at[6]); out->match_score_index = (int8_t*)(hb + out_at[7]);
-                } else {
-                    memcpy(out->n_hits, nh, (size_t)n_queries * 4);
-                    if (out->num_matched) memcpy(out->num_matched, hb + out_at[1], (size_t)n_queries * 8);
-                    for (uint32_t i = 0; i < n_queries; i++) {           // only the hits: slots behind n_hits[i] are undefined in the image too
-                        const size_t at = (size_t)i * KS, n = std::min<uint32_t>(nh[i], KS);
-                        memcpy(out->keys + at, hb + out_at[3] + at * 8, n * 8);
-                        memcpy(out->scores + at * 3, hb + out_at[4] + at * 24, n * 24);
-                        if (out->text_match) memcpy(out->text_match + at, hb + out_at[5] + at * 8, n * 8);
-                        if (out->vector_distance) memcpy(out->vector_distance + at, hb + out_at[6] + at * 4, n * 4);
-                        if (out->match_score_index) memcpy(out->match_score_index + at, hb + out_at[7] + at, n);
-                    }
-                }
-            } else {
-                TSGPU_HIP_TRY(hipMemcpyAsync(out->n_hits, o.n_hits, (size_t)n_queries * 4, hipMemcpyDeviceToHost, s));
-                if (out->num_matched) TSGPU_HIP_TRY(hipMemcpyAsync(out->num_matched, o.num_matched, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
-                TSGPU_HIP_TRY(hipMemcpyAsync(out->keys, o.keys, slots * 8, hipMemcpyDeviceToHost, s));
-                TSGPU_HIP_TRY(hipMemcpyAsync(out->scores, o.scores, slots * 24, hipMemcpyDeviceToHost, s));
-                if (out->text_match) TSGPU_HIP_TRY(hipMemcpyAsync(out->text_match, o.text_match, slots * 8, hipMemcpyDeviceToHost, s));
-                if (out->vector_distance) TSGPU_HIP_TRY(hipMemcpyAsync(out->vector_distance, o.vector_distance, slots * 4, hipMemcpyDeviceToHost, s));
-                if (out->match_score_index) TSGPU_HIP_TRY(hipMemcpyAsync(out->match_score_index, o.match_score_index, slots, hipMemcpyDeviceToHost, s));
-                TSGPU_HIP_TRY(hipMemcpyAsync(off_words.data(), o.off_words, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
-                TSGPU_HIP_TRY(hipStreamSynchronize(s));
-            }
-            for (uint32_t i = 0; i < n_queries; i++) out->status[i] = P.status[i];
-            if (out->search_cutoff) for (uint32_t i = 0; i < n_queries; i++) out->search_cutoff[i] = P.cutoff[i];
-        } else {
-            TSGPU_HIP_TRY(hipMemcpyAsync(out->status, P.status.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, s));
-            if (out->search_cutoff) TSGPU_HIP_TRY(hipMemcpyAsync(out->search_cutoff, P.cutoff.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, s));
-            TSGPU_HIP_TRY(hipMemcpyAsync(off_words.data(), o.off_words, (size_t)n_queries * 8, hipMemcpyDeviceToHost, s));
-            TSGPU_HIP_TRY(hipStreamSynchronize(s));
-        }
-        if (P.any_deadline) {                        // work items that ran out of time raised their query's flag: partial hits + search_cutoff
-            std::vector<uint32_t> cut(n_queries);
-            TSGPU_HIP_TRY(hipMemcpy(cut.data(), L.d_cut.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-            bool any = false;
-            for (uint32_t i = 0; i < n_queries; i++) if (cut[i]) { P.cutoff[i] = 1; any = true; }
-            if (any && out->search_cutoff) {
-                if (dev_out) TSGPU_HIP_TRY(hipMemcpy(out->search_cutoff, P.cutoff.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice));
-                else for (uint32_t i = 0; i < n_queries; i++) out->search_cutoff[i] = P.cutoff[i];
-            }
-        }
-        if (status_host) status_host->assign(P.status.begin(), P.status.end());
+        if ((rc = deliver(ctx, L, s, P, T.o, dev_out ? nullptr : &img, zero_copy, bo.alias_out, n_queries, out, off_words))) return rc;
+        if (bo.status_host) bo.status_host->assign(P.status.begin(), P.status.end());
         if (bo.cutoff_host) bo.cutoff_host->assign(P.cutoff.begin(), P.cutoff.end());
         const uint64_t t_synced = now_us();
 
-        // ---- bookkeeping: timings + algorithmic bytes ----
-        float ms_a = 0, ms_b = 0;
-        if (timing) (void)hipEventElapsedTime(&ms_a, L.ev[0], L.ev[1]);
-        if (timing) (void)hipEventElapsedTime(&ms_b, L.ev[1], L.ev[2]);
-        float ms_find = 0;
-        if (timing && find_marked && hit_groups == 1) (void)hipEventElapsedTime(&ms_find, L.ev[0], L.ev[3]);       // one find launch, then one score launch
-        uint64_t bytes = P.list_bytes;
-        if (!dev_out && out->num_matched) {
-            for (uint32_t i = 0; i < n_queries; i++) {
-                uint32_t n_num = 0;
-                if (DP.on) { for (uint32_t k = 0; k < queries[i].n_sort; k++) if (sort_kind_reads_key(queries[i].sort[k].kind)) n_num++; }
-                else for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (sort_kind_reads_key(P.q[i].sort_kind[k])) n_num++;
-                bytes += 4ull * off_words[i] + 8ull * out->num_matched[i] * n_num;
-            }
-        } else {
-            for (uint32_t i = 0; i < n_queries; i++) bytes += 4ull * off_words[i];
-        }
-        if (timing || bo.timing) {
-            std::lock_guard<std::mutex> tl(ctx->tm_mu);
-            ctx->timings.kw_search_ms = ms_a;
-            ctx->timings.kw_merge_ms = ms_b;
-            ctx->timings.kw_find_ms = ms_find;
-            ctx->timings.total_ms = ms_a + ms_b;
-            ctx->timings.kw_algorithmic_bytes = bytes;
-            ctx->kw_last_hit_groups = hit_groups;
-            ctx->kw_last_hit_records = hit_records;
-        }
-        if (count_touched) {
-            uint64_t c[8];
-            TSGPU_HIP_TRY(hipMemcpy(c, L.d_touched.p, sizeof(c), hipMemcpyDeviceToHost));
-            std::lock_guard<std::mutex> tl(ctx->tm_mu);
-            tsgpu_kw_touched& tt = ctx->kw_touched;
-            tt.find_driver_ids = c[0]; tt.find_metadata = c[1]; tt.find_tile_dma = c[2]; tt.find_probes = c[3]; tt.find_records = c[4];
-            tt.find_work_items = c[5]; tt.find_hit_records = c[6];
-            tt.find_requested_bytes = c[0] + c[1] + c[2] + c[3] + c[4];
-            // the score kernel's requests per hit record are fixed sizes (kw_score_kernel / load_runs_staged): the record itself, per token one
-            // BlockMeta (32 B), the offset_index pair (two 8-byte fetches) and the first offsets (8 B); per numeric sort key one column value; the
-            // rare third.. occurrence of a token in a document (one more 8-byte fetch each) is not counted
-            uint64_t sb = 0;
-            std::vector<uint64_t> nm_host;
-            const uint64_t* nm = !dev_out ? out->num_matched : nullptr;
-            if (dev_out && o.num_matched) {                          // (measurement only: one small read-back)
-                nm_host.resize(n_queries);
-                if (hipMemcpy(nm_host.data(), o.num_matched, (size_t)n_queries * 8, hipMemcpyDeviceToHost) == hipSuccess) nm = nm_host.data();
-            }
-            for (uint32_t i = 0; nm && !DP.on && i < n_queries; i++) {
-                uint32_t n_num = 0;
-                for (uint32_t k = 0; k < P.q[i].n_sort; k++) if (sort_kind_reads_key(P.q[i].sort_kind[k])) n_num++;
-                sb += nm[i] * (4ull * ((P.q[i].n_lists <= 3 ? 3 : KW_MAX_TOKENS) + 1) + 56ull * P.q[i].n_lists + 8ull * n_num);
-            }
-            tt.score_requested_bytes = sb;
-        }
-        // ---- matched ids (id_buff / all_result_ids, src/index.cpp:5549, 5565): every work item left an ascending segment ----
+        // ---- bookkeeping, the measurement read-back, the matched ids ----
+        const uint64_t* nm_host = dev_out ? nullptr : out->num_matched;
+        if (timing || bo.timing) record_timings(ctx, L, timing, st, H.records, P, DP.on, queries, off_words, nm_host);
+        if (count_touched && (rc = record_touched(ctx, L, P, DP.on, queries, n_queries, nm_host, dev_out ? T.o.num_matched : nullptr))) return rc;
         std::vector<uint32_t> ne;
         if (keep_ids && n_work && (bo.record_last || bo.id_lists)) {
             ne.resize(n_work);
-            TSGPU_HIP_TRY(hipMemcpy(ne.data(), part.n_emit, (size_t)n_work * 4, hipMemcpyDeviceToHost));
+            TSGPU_HIP_TRY(hipMemcpy(ne.data(), T.part.n_emit, (size_t)n_work * 4, hipMemcpyDeviceToHost));
         }
-        if (bo.record_last) {                        // legacy single-caller API (tsgpu_result_ids): remember where the segments live
-            L.last_ids_off.assign(n_queries, 0);
-            L.last_chunk_emit.assign(n_queries, {});
-            L.last_chunk_off.assign(n_queries, {});
-            L.last_ids_unsorted.assign(n_queries, 0);
-            if (keep_ids && n_work) {
-                for (uint32_t i = 0; i < n_queries; i++) {
-                    if (P.status[i] != TSGPU_OK || P.q[i].n_work == 0) continue;
-                    L.last_ids_off[i] = P.q[i].ids_out_off;
-                    L.last_chunk_emit[i].assign(ne.begin() + P.q[i].first_work, ne.begin() + P.q[i].first_work + P.q[i].n_work);
-                    L.last_chunk_off[i].resize(P.q[i].n_work);
-                    for (uint32_t c = 0; c < P.q[i].n_work; c++) L.last_chunk_off[i][c] = work[P.q[i].first_work + c].ids_out_off;
-                    L.last_ids_unsorted[i] = P.q[i].mf_index != KW_NONE;      // several driver lists: segments are sorted, their union is not
-                }
-            }
-        }
-        if (bo.id_lists) {
-            // per-call id lists: the segments are gathered into one dense array on the device (one launch, one download) and belong
-            // to THIS call — concurrent callers never see each other's ids
-            tsgpu_id_lists& il = *bo.id_lists;
-            il.begin.assign((size_t)n_queries + 1, 0);
-            std::vector<KwIdCopy> segs;
-            uint64_t at = 0;
-            for (uint32_t i = 0; i < n_queries; i++) {
-                il.begin[i] = at;
-                if (P.status[i] != TSGPU_OK || P.q[i].n_work == 0) continue;
-                for (uint32_t c = 0; c < P.q[i].n_work; c++) {
-                    const uint32_t cnt = ne[P.q[i].first_work + c];
-                    if (!cnt) continue;
-                    segs.push_back({P.q[i].ids_out_off + work[P.q[i].first_work + c].ids_out_off, at, cnt, 0u});
-                    at += cnt;
-                }
-            }
-            il.begin[n_queries] = at;
-            bool to_dev = bo.ids_dev != nullptr;              // the ids stay on the device, in the caller's buffer (several driver lists: the union is sorted on the host below)
-            for (uint32_t i = 0; to_dev && i < n_queries; i++) if (P.status[i] == TSGPU_OK && P.q[i].mf_index != KW_NONE) to_dev = false;
-            if (bo.ids_dev_done) *bo.ids_dev_done = to_dev;
-            if (to_dev) {
-                if (at) {
-                    if ((rc = bo.ids_dev->reserve(at * 4)) || (rc = upload(L.d_idseg, segs.data(), segs.size() * sizeof(KwIdCopy), s))) return rc;
-                    hipLaunchKernelGGL(kw_ids_gather_kernel, dim3((uint32_t)segs.size()), dim3(KW_THREADS), 0, s, (const uint32_t*)ids_out, L.d_idseg.as<KwIdCopy>(), bo.ids_dev->as<uint32_t>());
-                    TSGPU_HIP_TRY(hipGetLastError());
-                    TSGPU_HIP_TRY(hipStreamSynchronize(s));    // (the consumer runs on another stream)
-                }
-                at = 0;                                       // nothing to download
-            }
-            il.ids.resize(at);
-            if (at) {
-                if ((rc = L.d_idflat.reserve(at * 4)) || (rc = upload(L.d_idseg, segs.data(), segs.size() * sizeof(KwIdCopy), s))) return rc;
-                hipLaunchKernelGGL(kw_ids_gather_kernel, dim3((uint32_t)segs.size()), dim3(KW_THREADS), 0, s, (const uint32_t*)ids_out, L.d_idseg.as<KwIdCopy>(), L.d_idflat.as<uint32_t>());
-                TSGPU_HIP_TRY(hipGetLastError());
-                TSGPU_HIP_TRY(hipMemcpyAsync(il.ids.data(), L.d_idflat.p, at * 4, hipMemcpyDeviceToHost, s));
-                TSGPU_HIP_TRY(hipStreamSynchronize(s));
-                for (uint32_t i = 0; i < n_queries; i++)                      // several driver lists (query_by over several fields): ascending union
-                    if (P.q[i].mf_index != KW_NONE && P.status[i] == TSGPU_OK) std::sort(il.ids.begin() + il.begin[i], il.ids.begin() + il.begin[i + 1]);
-            }
-        }
+        if (bo.record_last) record_last_ids(L, P, work, ne, n_queries);
+        if (bo.id_lists && (rc = build_id_lists(L, s, P, work, ne, T.ids_out, n_queries, *bo.id_lists, bo.ids_dev, bo.ids_dev_done))) return rc;
         {
             const uint64_t t_end = now_us();
             ctx->kw_batches.fetch_add(1); ctx->kw_plan_us.fetch_add(t_planned - t_enter); ctx->kw_upload_us.fetch_add(t_uploaded - t_planned);
