@@ -130,6 +130,13 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * candidate kernels) with one load instead of two searches; built on the device by tsgpu_commit for the lists a write batch touched, within
  * the budget (longest lists first). min_ids = 0 switches them off (identical results). Any change takes effect at the next commit, which
  * re-packs the index. Counters: "kw_iddir_lists" (lists of the current snapshot that carry one), "kw_iddir_built" (built by commits so far),
+ * "kw_iddir_split_entries" (entries those builds marked IDDIR_SPLIT: block boundaries behind a PART-FILLED block, whose ids take the two-level
+ * search; a freshly packed list has none),
+ * "kw_find_dir_tile" = 1 (default) / "kw_find_dir_span_pct" (default 80; 1..2^20): stage 1 of the pair-find kernel answers "is the driver id in
+ * the second list, and where" from the second list's id directory, read per pair of driver blocks into an LDS tile (one LDS read per
+ * candidate instead of a block search and a slot search), in every work item whose second list carries a directory and whose pairs of driver
+ * blocks span on average at most span_pct % of the 28 672 doc ids one tile buffer covers; 0 = the tile of packed ids for every item
+ * (identical results),
  * "kw_two_kernels" = 1 (default): single-field queries run as a find kernel + a score kernel with hit records (seq_id + one
  * posting position per token) between them, 0: one fused kernel (identical results); "kw_hit_buffer_mb" = budget of that hit
  * buffer (default 20480; 16 bytes (<= 3 tokens) or 44 bytes per driver posting of the batch are reserved; a table of work items

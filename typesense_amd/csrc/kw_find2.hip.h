@@ -48,7 +48,7 @@ static const bool KW_F2_ROUNDS = TSGPU_F2_ROUNDS != 0;
 
 // COUNT = true: the kernel also COUNTS THE BYTES IT REQUESTS (every lane adds the width of each of its own loads / DMA words / stores to one of five
 // per-thread counters: driver ids, block metadata, tile DMA, third.. list probes, hit records; one wave reduction + five atomics per wave at the
-// end into IndexView::touched). A second instantiation launched only under option kw_count_touched — the timed kernel carries none of it.
+// end into IndexView::touched; slots 7..10: directory-mode work items, pairs, directory-tile pairs, pairs too wide for the tile). A second instantiation launched only under option kw_count_touched — the timed kernel carries none of it.
 // Same results either way (tests/test_emu_keyword.py runs both and compares).
 template <int TMAX, bool COUNT = false>
 __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQueryDev* __restrict__ queries, const KwWorkItem* __restrict__ work, const KwPartials& part,
@@ -60,6 +60,7 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
     const uint32_t t = threadIdx.x;
     const KwWorkItem wi = work[bid];
     uint32_t cb_ids = 0, cb_meta = 0, cb_tile = 0, cb_probe = 0, cb_rec = 0;      // COUNT only: bytes THIS lane requested
+    uint32_t cn_pairs = 0, cn_dir = 0, cn_wide = 0;                               // COUNT only (uniform): pairs searched; of them through a directory tile; too wide for it in a directory-mode item
     {
         const uint32_t* src = (const uint32_t*)(queries + wi.query);
         uint32_t* dst = (uint32_t*)&sq;
@@ -87,11 +88,6 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         if constexpr (COUNT) { if (slot < n) cb_ids += (m.n_ids_bits >> 16) == 16 ? 2u : 4u; }
         return (m.n_ids_bits >> 16) == 16 ? (uint32_t)((const uint16_t*)w)[s2] : w[s2];
     };
-    const uint32_t nB = T >= 2 ? dB.n_blocks : 0u;       // (no second list: every window slot is padding)
-    auto load_window = [&](uint32_t base) -> BlockIds {
-        if constexpr (COUNT) { if (base + lane < nB) cb_meta += 16; }
-        return base + lane < nB ? biB[base + lane] : PAD;
-    };
     // Driver-list metadata: lane j of every wave holds BlockIds[abase + j] — ONE vector load serves 32 pairs (most work items need only the
     // prologue's), a block's record is four v_readlane. (As per-pair loads they were uniform, so hipcc wanted them in SGPRs at once: a
     // global_load + s_waitcnt vmcnt(0) at the END of every iteration — a full memory round trip exposed per pair, which also drained the next
@@ -109,19 +105,53 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         return m;
     };
 
+    // DIRECTORY MODE, decided once per work item (uniform): where the second list carries an id directory (tsgpu_format.h) and the driver is dense
+    // — the item's pairs span on average at most ix.find_dir_span doc ids, a tile buffer's worth of directory entries — a pair's tile holds the
+    // slice of B's DIRECTORY under the pair instead of B's ids. "Is the driver id in B, and at which posting position" is then one LDS read, a
+    // bit test and pos + popcount (what probe_finish does with a global entry): no block search, no metadata reads, no slot search; the pair's
+    // plan is arithmetic on two ids: no window registers, no ballots, no bw_* arrays. An item is wholly one mode or the other (a window that
+    // re-centres after skipped pairs pays a uniform binary search in global memory). The directory does not care where a block's words live:
+    // LIST_HAS_BREAKS lists need no special case here.
+    uint32_t dmode = 0;
+    const uint32_t* __restrict__ tsrc = idwB;              // what the tile DMA copies: B's packed ids, or B's directory
+    if (T >= 2 && dB.dir_slot != 0 && ix.find_dir_span != 0) {
+        const uint32_t item_first = (uint32_t)__builtin_amdgcn_readlane((int)awin.first_id, 0), item_last = biA[wi.blk_end - 1].last_id;
+        const uint32_t pairs = (wi.blk_end - wi.blk_begin + 1) >> 1;
+        if constexpr (COUNT) { if (lane == 0) cb_meta += 16; }
+        if (item_last < ix.iddir_cap_ids && (unsigned long long)(item_last - item_first) <= (unsigned long long)ix.find_dir_span * pairs) {
+            dmode = 1;
+            tsrc = (const uint32_t*)(ix.iddir + (size_t)(dB.dir_slot - 1) * ix.iddir_slot_entries);
+        }
+    }
+    KW_UNIFORM_OPAQUE(dmode);
+    const uint32_t nB = (T >= 2 && !dmode) ? dB.n_blocks : 0u;       // (no second list / directory mode: every window slot is padding)
+    auto load_window = [&](uint32_t base) -> BlockIds {
+        if constexpr (COUNT) { if (base + lane < nB) cb_meta += 16; }
+        return base + lane < nB ? biB[base + lane] : PAD;
+    };
+
     uint32_t wbase = 0, wver = 0;
     BlockIds win = load_window(0), nxt = load_window(32);
     uint32_t win_dirty = 1;                               // (an integer, not a bool: a uniform bool lives in an SGPR PAIR as a lane mask)
-    struct Plan { uint32_t mode, rlo, rhi, w_begin, W, ver, base, buf; };   // mode: 0 tile, 1 tile in several rounds, 2 wide / broken run (probe), 3 exhausted, 4 no second list
+    struct Plan { uint32_t mode, rlo, rhi, w_begin, W, ver, base, buf; };   // mode: 0 tile, 1 tile in several rounds, 2 wide / broken run (probe), 3 exhausted, 4 no second list, 5 directory tile (rlo = its first entry)
     constexpr int PIPE_WORDS = KW_FIND_PIPE_WORDS;
     constexpr int TILE_WORDS = KW_FIND_TILE_WORDS;
     static_assert(TILE_WORDS == 2 * PIPE_WORDS * KW_THREADS, "two tile buffers: one searched, one being filled");
+    static_assert(PIPE_WORDS * KW_THREADS * 4 <= (int)KW_DIR_TILE_OVERREAD_BYTES, "a directory-tile fill reads at most this far past its slice");
     constexpr int HALF = PIPE_WORDS * KW_THREADS;
     uint32_t tbuf = 0;                                   // the buffer the last DMA went to
     // how the driver ids in [lo_id, hi_id] meet the second list; mode 0 also requests the tile
     auto make_plan = [&](uint32_t lo_id, uint32_t hi_id) -> Plan {
         Plan P; P.mode = 4; P.rlo = P.rhi = P.w_begin = P.W = 0; P.ver = wver; P.base = wbase; P.buf = 0;
         if (T < 2) return P;
+        if (dmode) {
+            // directory entries [lo_id >> 5, hi_id >> 5], two words each (8-byte entries: the 4-byte LDS-DMA words are aligned); a pair wider than
+            // the tile: one global directory load per candidate (mode 2)
+            P.rlo = lo_id >> 5;
+            P.w_begin = 2u * P.rlo;
+            P.W = 2u * ((hi_id >> 5) - P.rlo + 1u);
+            P.mode = 2;
+        } else {
         unsigned long long mk = __ballot(win.last_id >= lo_id ? 1 : 0);
         if (mk != 0 && (uint32_t)__builtin_ctzll(mk) >= 32) {          // cursor entered the upper half: slide by 32 blocks
             wbase += 32; win = nxt; nxt = load_window(wbase + 32); win_dirty = 1;
@@ -158,10 +188,12 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         P.w_begin = (uint32_t)__builtin_amdgcn_readlane((int)win.ids_woff, (int)P.rlo);
         const uint32_t nb_hi = (uint32_t)__builtin_amdgcn_readlane((int)win.n_ids_bits, (int)P.rhi);
         P.W = (uint32_t)__builtin_amdgcn_readlane((int)win.ids_woff, (int)P.rhi) + packed_words(nb_hi & 0xFFFF, nb_hi >> 16) - P.w_begin;
+        P.mode = KW_F2_ROUNDS ? 1 : 2;
+        }
         if (P.W <= (uint32_t)(PIPE_WORDS * KW_THREADS)) {
-            P.mode = 0;
+            P.mode = dmode ? 5 : 0;
             tbuf ^= 1; P.buf = tbuf;
-            const uint32_t* lane_src = idwB + P.w_begin + t;
+            const uint32_t* lane_src = tsrc + P.w_begin + t;
             uint32_t* lds_wave_base = sm.btile + tbuf * HALF + wave * 64;
 #if TSGPU_F2_MIDSLABS
             // (three fill sizes: the COUNT instantiation showed 10.5 of the find kernel's 17 GB of requests per 10 000-query batch to be tile DMA, two thirds of
@@ -175,7 +207,7 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
             else kw_glds_slabs<PIPE_WORDS>(lane_src, lds_wave_base);
             if constexpr (COUNT) cb_tile += 4u * (P.W <= 2u * KW_THREADS ? 2u : (uint32_t)PIPE_WORDS);
 #endif
-        } else P.mode = KW_F2_ROUNDS ? 1 : 2;
+        }
         return P;
     };
 
@@ -245,6 +277,7 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         bool ok0 = t < n0, ok1 = t < n1;
         const uint32_t id0 = ok0 ? a_first + araw0 : 0xFFFFFFFFu, id1 = ok1 ? b_first + araw1 : 0xFFFFFFFFu;
         const Plan C = P;
+        if constexpr (COUNT) { cn_pairs++; cn_dir += C.mode == 5 ? 1u : 0u; cn_wide += (dmode && C.mode == 2) ? 1u : 0u; }
         KW_PROF(0)
         const uint32_t* __restrict__ tile = sm.btile + C.buf * HALF;
         KW_F2_LOOP_BARRIER();
@@ -398,6 +431,26 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
                 if (!done1 && pos1 >= r_lo && pos1 <= r_hi) { slot_search(rt, id1, first1, nb1, woff[pos1] - w_begin, pos1, found1, p11); done1 = true; }
                 r_lo = r_hi + 1;
             }
+        } else if (C.mode == 5) {
+            // directory tile: the candidate's entry {pos, bits} from LDS (dropped-out candidates read entry 0: harmless)
+            const uint32_t k0 = ok0 ? 2u * ((id0 >> 5) - C.rlo) : 0u, k1 = ok1 ? 2u * ((id1 >> 5) - C.rlo) : 0u;
+            const uint2 e0 = make_uint2(tile[k0], tile[k0 + 1]), e1 = make_uint2(tile[k1], tile[k1 + 1]);
+            const uint32_t bit0 = 1u << (id0 & 31u), bit1 = 1u << (id1 & 31u);
+            const bool in0 = ok0 && (e0.y & bit0) != 0, in1 = ok1 && (e1.y & bit1) != 0;
+            const bool slow0 = in0 && (e0.x & IDDIR_SPLIT) != 0, slow1 = in1 && (e1.x & IDDIR_SPLIT) != 0;
+            p10 = e0.x + (uint32_t)__popc(e0.y & (bit0 - 1u)); p11 = e1.x + (uint32_t)__popc(e1.y & (bit1 - 1u));
+            found0 = in0 && !slow0; found1 = in1 && !slow1;
+            if (__ballot((slow0 || slow1) ? 1 : 0) != 0) {     // a block boundary behind a part-filled block (IDDIR_SPLIT): the two-level search, as probe_finish
+                const IndexView ixp = KW_RELOAD_VIEW(ix);
+                const ListDesc dBp = ixp.lists[q.list[q.probe_order[1]]];
+                if constexpr (COUNT) {
+                    if (slow0) found0 = probe_list<true>(ixp, dBp, id0, p10, &cb_probe);
+                    if (slow1) found1 = probe_list<true>(ixp, dBp, id1, p11, &cb_probe);
+                } else {
+                    if (slow0) found0 = probe_search(ixp, dBp, id0, p10);      // (what probe_finish does with a marked entry whose bit is set)
+                    if (slow1) found1 = probe_search(ixp, dBp, id1, p11);
+                }
+            }
         } else if (C.mode == 2) {
             const IndexView ixp = KW_RELOAD_VIEW(ix);   // (wide / broken runs: the view and the second list's descriptor re-read here)
             const ListDesc dBp = ixp.lists[q.list[q.probe_order[1]]];
@@ -476,6 +529,10 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
             if (lane == 0 && ix.touched) atomicAdd(ix.touched + k, (unsigned long long)c[k]);
         }
         if (t == 0 && ix.touched) { atomicAdd(ix.touched + 5, 1ull); atomicAdd(ix.touched + 6, (unsigned long long)qfn); }      // work items, hit records
+        if (t == 0 && ix.touched) {                                                                                            // directory mode: items, pairs
+            atomicAdd(ix.touched + 7, (unsigned long long)dmode); atomicAdd(ix.touched + 8, (unsigned long long)cn_pairs);
+            atomicAdd(ix.touched + 9, (unsigned long long)cn_dir); atomicAdd(ix.touched + 10, (unsigned long long)cn_wide);
+        }
     }
     KW_PROF(9)
     KW_PROF_FLUSH(ix.prof)

@@ -136,13 +136,14 @@ struct IndexView {
     uint32_t iddir_slot_entries;     // entries per slot (= ceil(iddir_cap_ids / 32))
     uint32_t iddir_cap_ids;          // doc ids the directories cover: [0, cap)
     unsigned long long* prof;        // TSGPU_PROF builds: 13 counters; else null
-    unsigned long long* touched;     // option kw_count_touched: 8 counters the COUNT instantiation of the find kernel adds its requested bytes to; else null
+    unsigned long long* touched;     // option kw_count_touched: 12 counters the COUNT instantiation of the find kernel adds its requested bytes to; else null
     const struct KwQueryMF* mf;      // multi-field queries of the batch (KwQueryDev::mf_index)
     uint32_t* fbits;                 // filtered multi-field queries: one bit per filter rank (KwQueryDev::fbits_off), zeroed per batch
     // in-flight deadline (search_cutoff, include/or_iterator.h:148-153): t0 = device wall clock when the batch started (stamped by
     // kw_stamp_kernel), ticks_per_us its rate; cutoff[query] is raised by the first work item that runs out of time
     const long long* t0;
     uint32_t ticks_per_us;
+    uint32_t find_dir_span;          // kw_find2_kernel, directory-tile stage 1: the widest mean pair span (doc ids) of a work item that takes it; 0 = never (option kw_find_dir_tile)
     uint32_t* cutoff;
     const SortKeyDesc* sort_keys;    // the context's key table, KW_SORT_KEY_SLOTS entries (KwQueryDev::sort_col of a TSGPU_SORT_EVAL slot indexes it; the planner checked the handle)
 };

@@ -72,6 +72,7 @@ IndexView make_view(tsgpu_ctx* ctx, const Snapshot& sn) {
     v.mf = nullptr;                                   // per lane: set by the batch
     v.fbits = nullptr;
     v.t0 = nullptr; v.ticks_per_us = 100; v.cutoff = nullptr;
+    v.find_dir_span = ctx->kw_find_dir_tile ? (uint32_t)(ctx->kw_find_dir_span_pct * (long long)(KW_FIND_PIPE_WORDS * KW_THREADS * 16) / 100) : 0u;      // (one tile buffer: 2 words per 32 doc ids)
     v.sort_keys = ctx->d_sort_keys.as<SortKeyDesc>();
     return v;
 }
@@ -372,6 +373,8 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "kw_candidates_rank_fold")) { ctx->kw_candidates_rank_fold = value != 0; return ok(); }
     if (!strcmp(name, "kw_mf_pipelined")) { ctx->kw_mf_pipelined = value != 0; return ok(); }
     if (!strcmp(name, "kw_count_touched")) { ctx->kw_count_touched = value != 0; return ok(); }
+    if (!strcmp(name, "kw_find_dir_tile")) { ctx->kw_find_dir_tile = value != 0; return ok(); }
+    if (!strcmp(name, "kw_find_dir_span_pct")) { ctx->kw_find_dir_span_pct = std::min<int64_t>(std::max<int64_t>(value, 1), 1 << 20); return ok(); }
     if (!strcmp(name, "kw_iddir_min_ids")) { ctx->kw_iddir_min_ids = value < 0 ? 0 : value; ctx->commit_force_full = true; return ok(); }
     if (!strcmp(name, "kw_iddir_density_div")) { ctx->kw_iddir_density_div = value < 1 ? 1 : value; ctx->commit_force_full = true; return ok(); }
     if (!strcmp(name, "kw_iddir_budget_mb")) { ctx->kw_iddir_budget_mb = value < 0 ? 0 : value; ctx->commit_force_full = true; return ok(); }
@@ -488,6 +491,13 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "kw_device_plans")) { *out = ctx->kw_device_plans.load(); return ok(); }                     // batches planned on the device / sent back to the host planner
     if (!strcmp(name, "kw_device_plan_fallbacks")) { *out = ctx->kw_device_plan_fallbacks.load(); return ok(); }
     if (!strcmp(name, "sort_keys_live")) { *out = ctx->sort_keys_live.load(); return ok(); }                         // tsgpu_sort_key_create_eval minus _destroy
+    // the last keyword batch run under option kw_count_touched: work items that took the find kernel's directory mode, pairs of driver blocks searched,
+    // of them through a directory tile, and pairs of directory-mode items too wide for the tile (probed per candidate)
+    if (!strcmp(name, "kw_find_dir_items")) { *out = ctx->kw_find_dir_items; return ok(); }
+    if (!strcmp(name, "kw_find_pairs")) { *out = ctx->kw_find_pairs; return ok(); }
+    if (!strcmp(name, "kw_find_dir_pairs")) { *out = ctx->kw_find_dir_pairs; return ok(); }
+    if (!strcmp(name, "kw_find_dir_wide_pairs")) { *out = ctx->kw_find_dir_wide_pairs; return ok(); }
+    if (!strcmp(name, "kw_iddir_split_entries")) { *out = ctx->kw_iddir_split_entries; return ok(); }               // IDDIR_SPLIT entries those builds wrote
     if (!strcmp(name, "kw_iddir_built")) { *out = ctx->kw_iddir_built; return ok(); }                               // id directories (re)built by commits so far
     if (!strcmp(name, "kw_iddir_lists")) { const auto sn = ctx->snapshot(); uint64_t n = 0; if (sn) for (const auto& r : sn->dir_of) n += r ? 1 : 0; *out = n; return ok(); }   // lists of the current snapshot that carry one
     if (!strcmp(name, "batch_exec_us")) { *out = ctx->batch_exec_us.load(); return ok(); }           // coalesced rounds: batch execution / hand-out to the callers
@@ -1522,8 +1532,8 @@ int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap,
     }
     v.cutoff = L.d_cut.as<uint32_t>();
     if (count_touched) {                         // measurement option: the find kernel's COUNT instantiation adds the bytes it requests here
-        if ((rc = L.d_touched.reserve(8 * 8))) return rc;
-        TSGPU_HIP_TRY(hipMemsetAsync(L.d_touched.p, 0, 8 * 8, s));
+        if ((rc = L.d_touched.reserve(12 * 8))) return rc;
+        TSGPU_HIP_TRY(hipMemsetAsync(L.d_touched.p, 0, 12 * 8, s));
         v.touched = L.d_touched.as<unsigned long long>();
     }
     const KwQueryDev* dq = T.dq; const KwWorkItem* dw = T.dw; const uint32_t* daux = T.daux; uint32_t* ids_out = T.ids_out;
@@ -1648,9 +1658,10 @@ void record_timings(tsgpu_ctx* ctx, KwLane& L, bool timing, const LaunchStats& s
 
 // measurement option kw_count_touched: the bytes the find kernel counted + the score kernel's, computed from the counts of matches
 int record_touched(tsgpu_ctx* ctx, KwLane& L, const Plan& P, bool dev_plan, const tsgpu_kw_query* queries, uint32_t n_queries, const uint64_t* nm, const uint64_t* nm_dev) {
-    uint64_t c[8];
+    uint64_t c[12];
     TSGPU_HIP_TRY(hipMemcpy(c, L.d_touched.p, sizeof(c), hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> tl(ctx->tm_mu);
+    ctx->kw_find_dir_items = c[7]; ctx->kw_find_pairs = c[8]; ctx->kw_find_dir_pairs = c[9]; ctx->kw_find_dir_wide_pairs = c[10];
     tsgpu_kw_touched& tt = ctx->kw_touched;
     tt.find_driver_ids = c[0]; tt.find_metadata = c[1]; tt.find_tile_dma = c[2]; tt.find_probes = c[3]; tt.find_records = c[4];
     tt.find_work_items = c[5]; tt.find_hit_records = c[6];

@@ -76,10 +76,17 @@ static const uint32_t LIST_HAS_BREAKS = 1u;
 //   {pos, bits}: bits = which of the ids [32w, 32w + 32) the list holds; pos = posting position (block * 256 + slot) of the lowest one.
 // "Is id x in the list, and where?" — what every probe of the third.. lists asks (posting_list_t::iterator_t::skip_to + the equality test of
 // or_iterator_t::intersect, /root/reference/src/or_iterator.cpp:20-79) — is ONE load: bit x & 31 of entry x >> 5, position = pos + popcount of
-// the lower bits (the ids of one entry are consecutive slots of one block). Entries whose ids straddle two blocks carry IDDIR_SPLIT in pos:
-// those (one per block, ~0.4 % of a list's ids) and ids beyond the pool's range take the regular two-level search. 8 bytes x num_docs / 32
+// the lower bits. The ids of one entry are consecutive posting positions also where they straddle two blocks, as long as the block in front of
+// the boundary is FULL: its last slot is position b * 256 + 255, the next block's slot 0 is (b + 1) * 256. Only an entry that straddles a boundary
+// behind a PART-FILLED block (incremental commits leave those; a freshly packed list has none but its last block) carries IDDIR_SPLIT in pos:
+// a probe that finds its bit set there, and ids beyond the pool's range, take the regular two-level search. (Marking every boundary — one entry
+// per block, ~0.4 % of a list's ids — put a lane of most 256-survivor probe batches into that search, a dozen dependent loads the whole
+// workgroup waits for: 12 % of the find kernel's time on the 10 000-query batch, profiles/r10/exp_find2_dir_tile.txt.) 8 bytes x num_docs / 32
 // per list (2.8 MB at 10M documents), built on the device by index_iddir_build_kernel at commit time.
 static const uint32_t IDDIR_SPLIT = 0x80000000u;
+// The find kernel's stage 1 reads a pair's slice of the second list's directory from an LDS tile (kw_find2.hip.h: one 7 KB tile buffer holds 896
+// entries = 28 672 doc ids); the fill reads up to a buffer past the slice, so the directory pool is allocated this much larger
+static const uint32_t KW_DIR_TILE_OVERREAD_BYTES = 8192;
 
 TSGPU_HD static inline uint32_t required_bits(uint32_t v) {   // include/array_base.h:23-25
     return v == 0 ? 0u : 32u - (uint32_t)__builtin_clz(v);

@@ -551,6 +551,7 @@ struct tsgpu_ctx {
     uint32_t kw_merge_select_min = 2;                // queries with at least this many partial lists are merged by selection (kw_select_partials: tree merge); 0 = always fold
     bool kw_count_touched = false;                   // measurement option: keyword batches launch the byte-counting instantiation of the find kernel
     tsgpu_kw_touched kw_touched{};                   // ... and leave its counters here (tsgpu_kw_last_touched; under tm_mu)
+    uint64_t kw_find_dir_items = 0, kw_find_pairs = 0, kw_find_dir_pairs = 0, kw_find_dir_wide_pairs = 0;     // ... and the directory-mode counts (tsgpu_get_counter; under tm_mu)
     std::atomic<uint64_t> kw_mf_pipelined_launches{0}, kw_candidates_rank_launches{0};
     bool kw_candidates_rank_fold = true;             // candidate combinations: the sort-free fold (kw_candidates_rank_kernel) instead of two bitonic sorts
     bool kw_mf_pipelined = true;                     // multi-field find kernel: the pipelined form for launches of <= 2 query_by fields (kw_find_mf2.hip.h)
@@ -561,6 +562,9 @@ struct tsgpu_ctx {
     long long kw_iddir_density_div = 64;
     long long kw_iddir_budget_mb = 4096;             // device memory for the directory pool (longest lists first)
     uint64_t kw_iddir_built = 0;                     // counter: directories (re)built by commits
+    uint64_t kw_iddir_split_entries = 0;             // counter: IDDIR_SPLIT entries those builds wrote (block boundaries behind a part-filled block)
+    bool kw_find_dir_tile = true;                    // find kernel, stage 1: work items over a dense driver read the second list's id directory from LDS tiles (kw_find2.hip.h)
+    long long kw_find_dir_span_pct = 80;             // ... where the item's mean pair spans at most this share of the 28 672 doc ids one tile buffer's entries cover
     bool kw_two_kernels = true;                      // queries of <= 3 tokens: find kernel + score kernel instead of the fused kernel
     uint32_t kw_device_plan_min_queries = 512;       // batches of plain single-field queries from this size on are planned ON THE DEVICE (kw_plan.hip.h); 0 = always on the host
     std::atomic<uint64_t> kw_device_plans{0}, kw_device_plan_fallbacks{0};

@@ -358,10 +358,13 @@ __global__ void index_desc_scatter_kernel(const uint64_t* __restrict__ dst, cons
 struct IdDirJob { uint64_t ids_base; uint64_t first_block; uint32_t blk_base, n_blocks, slot, pad; };      // first_block: prefix of n_blocks over the jobs
 
 // one workgroup per posting block of a list that gets a (new) directory; thread t = slot t: sets its id's bit, and the entry's position if
-// it is the lowest id of its entry; an entry that also holds ids of the previous block is marked IDDIR_SPLIT. (atomicOr on zeroed memory:
-// every writer of an entry agrees with every other.)
+// it is the lowest id of its entry. An entry that also holds ids of the previous block is marked IDDIR_SPLIT only where that block is
+// PART-FILLED: behind a full block (slot 255 = position b * 256 - 1) this block's slot 0 is the next posting position, so pos + popcount is
+// exact across the boundary and the entry stays plain (every boundary of a freshly packed list). split_entries counts the entries marked.
+// (atomicOr on zeroed memory: every writer of an entry agrees with every other.)
 __global__ __launch_bounds__(256) void index_iddir_build_kernel(const IdDirJob* __restrict__ jobs, uint32_t n_jobs, const BlockIds* __restrict__ blk_ids,
-                                                                const uint32_t* __restrict__ ids_payload, uint2* __restrict__ dir, uint32_t slot_entries, uint32_t cap_ids) {
+                                                                const uint32_t* __restrict__ ids_payload, uint2* __restrict__ dir, uint32_t slot_entries, uint32_t cap_ids,
+                                                                unsigned long long* __restrict__ split_entries) {
     const uint64_t gb = blockIdx.x;
     uint32_t lo = 0, hi = n_jobs - 1;
     while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (jobs[mid].first_block <= gb) lo = mid; else hi = mid - 1; }
@@ -377,8 +380,9 @@ __global__ __launch_bounds__(256) void index_iddir_build_kernel(const IdDirJob* 
     unsigned int* e = (unsigned int*)(dir + (size_t)j.slot * slot_entries + (id >> 5));
     bool lowest;
     if (t == 0) {
-        const bool shared = b > 0 && (blk_ids[j.blk_base + b - 1].last_id >> 5) == (id >> 5);
-        if (shared) atomicOr(e, IDDIR_SPLIT);
+        bool shared = false, part = false;
+        if (b > 0) { const BlockIds pm = blk_ids[j.blk_base + b - 1]; shared = (pm.last_id >> 5) == (id >> 5); part = (pm.n_ids_bits & 0xFFFF) < BLOCK_IDS; }
+        if (shared && part && !(atomicOr(e, IDDIR_SPLIT) & IDDIR_SPLIT)) atomicAdd(split_entries, 1ull);
         lowest = !shared;
     } else lowest = ((m.first_id + (w16 ? (uint32_t)((const uint16_t*)w)[t - 1] : w[t - 1])) >> 5) != (id >> 5);
     if (lowest) atomicOr(e, b * (uint32_t)BLOCK_IDS + t);
@@ -414,7 +418,8 @@ int build_id_directories(tsgpu_ctx* ctx, Snapshot& s, const Snapshot* cur, const
         if (n_slots == 0) return TSGPU_OK;
         pool = std::make_shared<IdDirPool>();
         pool->bin = ctx->retire_bin;
-        if (pool->buf.reserve(n_slots * slot_bytes) != TSGPU_OK) { tls_error().clear(); return TSGPU_OK; }
+        // (+ 8 KB: the find kernel's directory-tile fill reads up to a tile past a pair's slice, kw_find2.hip.h — into the next slot or into this padding)
+        if (pool->buf.reserve(n_slots * slot_bytes + KW_DIR_TILE_OVERREAD_BYTES) != TSGPU_OK) { tls_error().clear(); return TSGPU_OK; }
         pool->cap_ids = (uint32_t)cap; pool->slot_entries = (uint32_t)(cap / 32); pool->n_slots = (uint32_t)n_slots;
         for (uint32_t i = (uint32_t)n_slots; i-- > 0;) pool->free_slots.push_back(i);
     }
@@ -436,20 +441,25 @@ int build_id_directories(tsgpu_ctx* ctx, Snapshot& s, const Snapshot* cur, const
     if (!jobs.empty()) {
         if (total_blocks > 0x7FFFFFFFull) { s.dir_of.clear(); return TSGPU_OK; }
         DevBuf d_jobs;
-        int rc = d_jobs.reserve(jobs.size() * sizeof(IdDirJob));
+        int rc = d_jobs.reserve((jobs.size() + 1) * sizeof(IdDirJob));                  // (+ one record's room: the kernel's split-entry counter)
         if (rc != TSGPU_OK) { s.dir_of.clear(); tls_error().clear(); return TSGPU_OK; }
+        unsigned long long* d_splits = (unsigned long long*)(d_jobs.as<IdDirJob>() + jobs.size());
+        unsigned long long n_splits = 0;
         hipError_t e = hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(IdDirJob), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemsetAsync(d_splits, 0, sizeof(unsigned long long), ctx->stream);
         for (size_t i = 0; i < jobs.size() && e == hipSuccess; i++)
             e = hipMemsetAsync(pool->buf.as<uint2>() + (size_t)jobs[i].slot * pool->slot_entries, 0, (size_t)pool->slot_entries * sizeof(uint2), ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(index_iddir_build_kernel, dim3((uint32_t)total_blocks), dim3(256), 0, ctx->stream, d_jobs.as<IdDirJob>(), (uint32_t)jobs.size(), s.ar->blk_ids.as<BlockIds>(),
-                               s.ar->ids_payload.as<uint32_t>(), pool->buf.as<uint2>(), pool->slot_entries, pool->cap_ids);
+                               s.ar->ids_payload.as<uint32_t>(), pool->buf.as<uint2>(), pool->slot_entries, pool->cap_ids, d_splits);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = hipMemcpy(&n_splits, d_splits, sizeof(n_splits), hipMemcpyDeviceToHost);
         }
         d_jobs.release();
         if (e != hipSuccess) { s.dir_of.clear(); return fail(TSGPU_ERR_DEVICE, std::string("tsgpu_commit: id directories: ") + hipGetErrorString(e)); }
         ctx->kw_iddir_built += jobs.size();
+        ctx->kw_iddir_split_entries += n_splits;
     }
     s.dir_pool = pool;
     for (size_t h = 0; h < s.dir_of.size(); h++) if (s.dir_of[h]) s.h_lists[h].dir_slot = s.dir_of[h]->slot + 1;
