@@ -562,10 +562,14 @@ int tsgpu_vec_hnsw_export(tsgpu_ctx* ctx, uint32_t vec_field_id, int32_t info[4]
 /* up to k (distance, label) per query, closest first, found by greedy descent + the ef-bounded best-first search of layer 0
  * (max(ef, k) candidates). functor_present: the caller passes a filter functor (Typesense always does) — it selects hnswlib's
  * stricter stop rule; allow_ids (sorted, NULL = all) / excluded_ids / deleted labels are what the functor and isMarkedDeleted
- * reject. One wavefront per query, up to 4 096 queries in flight (16-bit visited tags per query slot, 16 GiB at most); the heaps
- * live in LDS sized by max(ef, k) (<= 128 / 512 / 1024; max(ef, k) > 1024 -> 501), a batch in which a candidate heap outgrows a small
- * size runs again on the largest. n_out[q] == 0xFFFFFFFF: the candidate heap outgrew even that (4 096 entries) — run the query
- * with tsgpu_vec_knn_batch. Counters "hnsw_last_expansions" / "hnsw_last_distances": layer-0 totals of the last batch. */
+ * reject. One wavefront per query, up to 4 096 queries in flight. Visited bookkeeping: one hash set of ids per query in flight (default; 8 192 ..
+ * 65 536 words by tier, independent of the row count), or, with option "hnsw_visited_hash" = 0, hnswlib-style 16-bit tags per row and query slot
+ * (option "hnsw_visited_max_gib", 64 by default, caps that array by lowering the queries in flight). The heaps live in LDS sized by max(ef, k): four
+ * tiers, <= 128 / 256 / 512 / 1024 (max(ef, k) > 1024 -> 501). The queries — and only those — whose candidate heap or visited set outgrows a
+ * smaller tier run again on the largest; a visited set that passes half full even there runs again with a set 8x, then 64x as large (counter
+ * "hnsw_tier_reruns": queries run again, one per query and re-run). n_out[q] == 0xFFFFFFFF: the candidate heap outgrew the largest tier
+ * (4 096 entries), or the visited set the 64x one — run the query with tsgpu_vec_knn_batch. Counters "hnsw_last_expansions" /
+ * "hnsw_last_distances": layer-0 totals of the last batch. */
 int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
                                 int functor_present, const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids,
                                 uint32_t n_excluded, float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out);

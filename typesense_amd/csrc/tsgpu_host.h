@@ -581,6 +581,10 @@ struct tsgpu_ctx {
     uint64_t vec_prefilter_groups = 0;               // query groups answered by the bf16 bracket path
     int hnsw_test_tiny_cand = 0;                      // TESTS ONLY (option "hnsw_test_tiny_cand"): searches with max(ef, k) <= 128 start on a 24-entry candidate heap, so that
                                                      // the re-run of the overflowed queries on the largest tier is exercised on small graphs
+    uint32_t hnsw_test_slots = 0;                    // TESTS ONLY (option "hnsw_test_slots"): when non-zero, caps the concurrent query slots of an HNSW search (4 096
+                                                     // otherwise), in both visited modes, so that a block serves several queries in a batch of a few
+    uint32_t hnsw_test_epoch = 0;                    // TESTS ONLY (option "hnsw_test_epoch"): when non-zero, the next tag-mode launch starts from this tag epoch, once (the
+                                                     // clear of the tags at epoch 0xFFF0 is reached without 65 000 queries per slot)
     uint64_t hnsw_tier_reruns = 0;                   // queries that were run again on the largest tier since the context was created (counter "hnsw_tier_reruns")
     int hnsw_visited_hash = 1;                        // 1 = per-query hash sets of visited ids (default), 0 = 16-bit tags per row and concurrent query
     int hnsw_visited_max_gib = 64;                    // cap of one field's HNSW visited-tag array (option): bounds the queries traversing concurrently

@@ -878,6 +878,7 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
     int rc;
     const bool hash_mode = ctx->hnsw_visited_hash != 0;
     uint32_t slots = f->g_slots;
+    if (ctx->hnsw_test_slots) slots = std::min(slots, ctx->hnsw_test_slots);      // TESTS ONLY: a block serves several queries in a small batch
     if (!hash_mode) {
         // tag mode: one uint16 per row and concurrent query (hnswlib's VisitedListPool); option hnsw_visited_max_gib caps the array
         while (slots > 32 && (uint64_t)slots * std::max<uint32_t>(f->g_n, 1) * 2 > ((uint64_t)ctx->hnsw_visited_max_gib << 30)) slots >>= 1;
@@ -886,6 +887,7 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
             TSGPU_HIP_TRY(hipMemsetAsync(f->g_visited.p, 0, (size_t)slots * std::max<uint32_t>(f->g_n, 1) * 2 + 64, s));
             f->g_tag_slots = slots; f->g_epoch = 1;
         }
+        if (ctx->hnsw_test_epoch) { f->g_epoch = ctx->hnsw_test_epoch; ctx->hnsw_test_epoch = 0; }      // TESTS ONLY: as if that many queries per slot had run before
     }
     const uint32_t grid = std::min<uint32_t>(n_q, slots);
     const size_t tag_bytes = ((size_t)slots * f->g_n * 2 + 7) & ~(size_t)7;
@@ -902,7 +904,8 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
     // LDS tier by max(ef, k): result heap 128 / 256 / 512 / 1024 entries, candidate heap 1024 / 1024 / 2048 / 4096 = 13.6 / 14.6 / 25 / 45 KB of LDS per query
     // = 11 / 10 / 6 / 3 queries in flight per CU (the 256 tier — round 6 — is the bulk build's: ef_construction 200 ran on the 512 tier's six before). The
     // queries whose candidate heap (or visited set) outgrows their tier — and only those — run again on the largest (round 6: before, one of them sent the
-    // whole batch there). Smaller candidate heaps for the upper tiers were measured and lose: at ef 400 / 800 most queries outgrow 1024 / 2048 entries
+    // whole batch there). On the largest tier a candidate-heap overflow is final (n_out = 0xFFFFFFFF); the queries whose visited SET passed half full there
+    // — the kernel counts and marks the two causes apart — run again with larger sets. Smaller candidate heaps for the upper tiers were measured and lose: at ef 400 / 800 most queries outgrow 1024 / 2048 entries
     // (10M x 768: 105 K -> 48 K q/s, 31 K -> 26 K q/s with the re-runs).
     const uint32_t need = std::max(k, ef);
     int tier = need <= 128 ? 0 : (need <= 256 ? 1 : (need <= 512 ? 2 : 3));
@@ -922,6 +925,7 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
             grid_now = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid_t, (8ull << 30) / ((uint64_t)vs * 4)));
             if ((rc = f->g_vhash.reserve((size_t)grid_now * vs * 4))) return rc;
             a.vhash = f->g_vhash.as<uint32_t>(); a.vhash_slots = vs;
+            a.set_full_mark = (tier == TOP && vs_boost >= 64) ? 0xFFFFFFFFu : VEC_HNSW_SET_FULL;      // the last attempt reports to the caller
         } else {
             grid_now = grid_t;
             if ((uint64_t)f->g_epoch + iters_t >= 0xFFF0ull) {      // tag space exhausted: clear the tags
@@ -952,14 +956,18 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
 #endif
         tot_exp += (uint64_t)h_stat[2] | ((uint64_t)h_stat[3] << 32);
         tot_dist += (uint64_t)h_stat[4] | ((uint64_t)h_stat[5] << 32);
-        if (!h_stat[0]) break;
-        if (tier == TOP && !(hash_mode && vs_boost < 64)) break;      // (a candidate heap beyond the largest tier: those queries report n_out = 0xFFFFFFFF)
-        // which queries: the ones marked 0xFFFFFFFF (of this launch's selection, or of the whole batch the first time)
+        const uint32_t heap_over = h_stat[0], set_over = h_stat[1];      // queries of this launch: candidate heap beyond CANDCAP / visited set past half full
+        if (!heap_over && !set_over) break;
+        // the largest tier: a candidate heap beyond it is final (those queries report n_out = 0xFFFFFFFF; a larger visited set cannot help them), a full set
+        // runs again 8x / 64x as large
+        if (tier == TOP && (!set_over || vs_boost >= 64)) break;
+        // which queries (of this launch's selection, or of the whole batch the first time): below the largest tier both marks, on it the full sets only
         h_cnt.resize(n_q);
         TSGPU_HIP_TRY(hipMemcpy(h_cnt.data(), d_cnt, (size_t)n_q * 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> again;
-        if (h_sel.empty()) { for (uint32_t q = 0; q < n_q; q++) if (h_cnt[q] == 0xFFFFFFFFu) again.push_back(q); }
-        else for (uint32_t q : h_sel) if (h_cnt[q] == 0xFFFFFFFFu) again.push_back(q);
+        auto marked = [&](uint32_t q) { return h_cnt[q] == VEC_HNSW_SET_FULL || (tier < TOP && h_cnt[q] == 0xFFFFFFFFu); };
+        if (h_sel.empty()) { for (uint32_t q = 0; q < n_q; q++) if (marked(q)) again.push_back(q); }
+        else for (uint32_t q : h_sel) if (marked(q)) again.push_back(q);
         if (again.empty()) break;
         h_sel.swap(again);
         if ((rc = f->g_sel.reserve(h_sel.size() * 4))) return rc;

@@ -1312,13 +1312,15 @@ struct VecHnswArgs {
     uint16_t* visited; uint32_t epoch_base;             // tag mode: [slots][n_rows] 16-bit tags (hnswlib's VisitedList is 16-bit, too); slot = blockIdx.x
     // hash mode (default): the ids a query visits (a few thousand) live in ITS open-addressing set of vhash_slots words (a power of two,
     // 64 x the tier's heap capacity), cleared per query — memory per concurrent query no longer depends on the row count (16-bit tags:
-    // 2 B x rows, 41 GB for 2 048 queries at 10M rows; sets: 32 KB - 256 KB each). A set that fills beyond half reports the query like a
-    // candidate-heap overflow (re-run on the largest tier, then exactly by the caller).
-    uint32_t* vhash; uint32_t vhash_slots;
-    uint32_t* overflow_cnt;                             // [0] queries whose candidate heap outgrew CANDCAP; [1..2] u64 expansions, [3..4] u64 distances (batch totals)
+    // 2 B x rows, 41 GB for 2 048 queries at 10M rows; sets: 32 KB - 256 KB each). A query whose set would fill beyond half stops and is
+    // marked n_out = set_full_mark: VEC_HNSW_SET_FULL while the host still has a larger set to offer (only a larger SET helps such a
+    // query, only a larger HEAP one whose candidate heap overflowed: the host tells them apart), 0xFFFFFFFF on the last attempt.
+    uint32_t* vhash; uint32_t vhash_slots; uint32_t set_full_mark;
+    uint32_t* overflow_cnt;                             // [0] queries whose candidate heap outgrew CANDCAP; [1] queries whose visited set passed half full; [2..3] u64 expansions, [4..5] u64 distances (batch totals)
     const uint64_t* labels;                             // nullable: internal ids come back
     float* dist_out; uint64_t* label_out; uint32_t* n_out;   // [n_q][k]; n_out = 0xFFFFFFFF: candidate heap overflow (caller re-runs exactly)
 };
+static const uint32_t VEC_HNSW_SET_FULL = 0xFFFFFFFEu;   // n_out between the launches of one search only: never handed to the caller
 #ifndef TSGPU_HNSW_ROWS
 #define TSGPU_HNSW_ROWS 4
 #endif
@@ -1467,7 +1469,7 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
         const uint32_t ef = a.ef > a.k ? a.ef : a.k;
         HnswHeap top{top_e, 0}, cand{cand_e, 0};
         float lowerBound;
-        bool overflow = false;
+        bool overflow = false, set_full = false;
         uint32_t n_exp = 0, n_dist = 0;
 #ifdef TSGPU_HNSW_PROF          // tools/ builds: wall-clock ticks (100 MHz) per phase of the layer-0 loop, batch totals behind the statistics
         unsigned long long pt[4] = {0, 0, 0, 0}, pl = wall_clock64();
@@ -1504,9 +1506,9 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
             // (count and ids requested together: a record has 1 + 2M words whatever its count; ids past the count are ignored)
             const uint32_t cw = lst[lane < lw - 1 ? 1 + lane : 0];
             // the set stays at most half full (n_dist counts every first visit but the entry point's; a list adds at most cnt): a query that
-            // would outgrow it stops here and is reported like a candidate-heap overflow
+            // would outgrow it stops here and is reported as such (overflow_cnt[1], n_out = set_full_mark)
             const bool room = !vset || n_dist + 1 + cnt <= a.vhash_slots / 2;
-            if (!room && lane == 0) { overflow = true; cand.n = 0; }
+            if (!room && lane == 0) { set_full = true; cand.n = 0; }
             if (room && lane < cnt) { c = cw; fresh = visit(c, epoch, n_vis); }
             const unsigned long long m = __ballot(fresh ? 1 : 0);
             const uint32_t nf = (uint32_t)__popcll(m);
@@ -1554,6 +1556,7 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
             atomicAdd((unsigned long long*)(a.overflow_cnt + 2), (unsigned long long)n_exp);
             atomicAdd((unsigned long long*)(a.overflow_cnt + 4), (unsigned long long)n_dist);
             if (overflow) { a.n_out[q] = 0xFFFFFFFFu; atomicAdd(a.overflow_cnt, 1u); }
+            else if (set_full) { a.n_out[q] = a.set_full_mark; atomicAdd(a.overflow_cnt + 1, 1u); }
             else {
                 while (top.n > a.k) top.pop();
                 uint32_t sz = top.n;
