@@ -177,7 +177,11 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * request threads need the cores; hipEventSynchronize on a blocking-sync event still spins inside the runtime);
  * "hnsw_visited_hash" = 1 (default): an HNSW traversal keeps the ids it has visited in a per-query hash set (32-256 KB, whatever the
  * row count; up to 4096 queries traverse at once), 0: 16-bit tags per row and concurrent query, capped by
- * "hnsw_visited_max_gib" (default 64, 1..128: 2 bytes x rows x concurrent queries — 41 GB for 2048 queries at 10M rows) */
+ * "hnsw_visited_max_gib" (default 64, 1..128: 2 bytes x rows x concurrent queries — 41 GB for 2048 queries at 10M rows);
+ * TESTS ONLY: "kw_plan_digest" = 1 (default 0): every keyword / wildcard batch leaves two 64-bit FNV-1a digests of its PLAN in the counters
+ * "kw_last_plan_cut_digest" (per query: status, handles, probe order, work items, merge sources) and "kw_last_plan_layout_digest" (offsets, table
+ * sizes, merge groups, hit-buffer offsets) — taken over fields, not struct bytes, and over no pointer; a plan made on the device is read back for
+ * it. Any valid plan gives the same hits; the digests let the tests see the plan itself (csrc/kw_plan_digest.h). Off: one branch per batch. */
 int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
 /* introspection counters (tests / bench): "vec_overflow_rounds", "vec_prefilter_groups", "vec_prefilter_fallbacks",
  * "vec_rescored_rows", "vec_candidate_rows" (rows of the last bracket group that reached the exact re-score / that passed the scan's tile-level bound),
@@ -185,7 +189,7 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
  * "batch_rounds" / "batch_coalesced_calls" (micro-batcher: rounds executed / calls they served; "gb_batch_rounds" / "gb_batch_coalesced_calls": of grouped calls), host phase totals in us over all
  * keyword batches ("kw_batches", "kw_plan_us", "kw_upload_us", "kw_launch_us", "kw_wait_us", "kw_book_us", "batch_exec_us",
  * "batch_scatter_us") and over all coalesced calls ("kw_queue_us" = parked -> its round starts, "kw_wake_us" = results ready ->
- * the caller runs again) */
+ * the caller runs again), "kw_last_plan_cut_digest" / "kw_last_plan_layout_digest" (the last batch under option "kw_plan_digest") */
 int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out);
 /* bytes of HBM held by the context's index mirrors */
 uint64_t tsgpu_device_bytes(tsgpu_ctx* ctx);

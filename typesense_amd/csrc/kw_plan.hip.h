@@ -6,7 +6,8 @@
 // filter / hidden ids / dropped tokens / deadline — every one of those steps is data-parallel over the queries, and 10 000 of them cost
 // the host ~0.5 ms on eight threads (more where N ranks share a node's cores): three small kernels do the same from a 64-byte record per
 // query. ANY valid plan yields the same results (scores depend on the document only, sort keys are total orders: DESIGN.md §3.1), so the
-// device planner reproduces the host planner's policy (chunk rule, cost model, heaviest first) but is not required to match it bit for bit.
+// device planner is not required to match the host planner bit for bit: it computes the cost key in float and applies none of the rules for small
+// batches. The policy itself (chunk rule, cost model, who needs merge groups) is written once, in kw_plan_policy.h, and called from both.
 // Batches with any other query shape keep the host planner.
 //
 //   kw_plan_resolve_kernel : one thread per query — term ids -> list handles (device mirror of HandleMaps::dense_handle), list lengths,
@@ -17,6 +18,7 @@
 //                            and hit-buffer blocks in that order, accumulated with atomics
 //   kw_plan_emit_kernel    : one thread per query — first_work / n_work, its work items and their hit offsets
 #pragma once
+#include "kw_plan_policy.h"
 
 namespace tsgpu {
 
@@ -142,38 +144,20 @@ __global__ __launch_bounds__(256) void kw_plan_resolve_kernel(KwPlanParams pp, c
 __global__ __launch_bounds__(256) void kw_plan_chunk_kernel(KwPlanParams pp, const KwQueryDev* __restrict__ q, KwPlanScratch sc, KwPlanTotals* __restrict__ tot) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < pp.n_queries;
-    // the batch-wide chunk (plan_batch: a few thousand work items, >= 3 per resident workgroup slot, without fragmenting the queries)
-    uint32_t CH = pp.chunk_blocks_opt;
-    if (CH == 0) {
-        const unsigned long long c = tot->total_best_blocks / 3000;
-        CH = 16;
-        while (CH < pp.max_chunk && (unsigned long long)CH * 2 <= c) CH *= 2;
-    }
+    // (the policy — batch chunk, per-query chunk, cost key, who needs merge groups — is kw_plan_policy.h's, shared with plan_batch)
+    const uint32_t CH = pp.chunk_blocks_opt ? pp.chunk_blocks_opt : kw_policy_batch_chunk(tot->total_best_blocks, pp.max_chunk, KW_POLICY_LARGE_BATCH, pp.merge_select_min);
     uint32_t cnt = 0, nb = 0, tab = 0;
     if (live) {
         nb = sc.n_blocks[i];
         const uint32_t nl = q[i].n_lists;
         tab = nl <= 3 ? 0u : 1u;
-        uint32_t chunk_q = CH;
-        if (pp.chunk_blocks_opt == 0 && nb) {
-            const uint32_t per = (nb + pp.max_partials - 1) / pp.max_partials;
-            const uint32_t c2 = per < 256u ? per : 256u;
-            chunk_q = chunk_q > c2 ? chunk_q : c2;
-        }
-        cnt = nb ? (nb + chunk_q - 1) / chunk_q : 0;
-        // launch-order key: the query's LARGEST work item = driver blocks x (fixed + |B|/|A| + third-list probes of the stage-1 survivors)
-        const float la = (float)(sc.len_a[i] ? sc.len_a[i] : 1u);
-        float r = nl >= 2 ? (float)sc.len_b[i] / la : 0.0f;
-        r = r < 64.0f ? r : 64.0f;
-        const float surv = nl >= 3 ? 256.0f * (float)sc.len_b[i] / (float)(pp.num_docs ? pp.num_docs : 1u) : 0.0f;
-        const float cost = (float)(chunk_q < nb ? chunk_q : nb) * (pp.cost_fixed + pp.cost_r * r + pp.cost_probe * surv);
+        const uint32_t chunk_q = kw_policy_query_chunk(CH, pp.chunk_blocks_opt == 0, nb, kw_policy_max_partials(pp.max_partials, nb, KW_POLICY_LARGE_BATCH, 0));
+        cnt = kw_policy_item_count(nb, chunk_q);
+        const float cost = kw_policy_item_cost<float>(chunk_q, nb, nl, sc.len_a[i], sc.len_b[i], pp.num_docs, pp.cost_fixed, pp.cost_r, pp.cost_probe);
         sc.cnt[i] = cnt;
         sc.chunk[i] = chunk_q;
         sc.key[i] = ((unsigned long long)tab << 32) | (0xFFFFFFFFu - __float_as_uint(cost));
-        // more partial lists than the selecting merge takes (or the selecting merge switched off and more than two groups of eight): the
-        // host planner's two-level merge groups are needed
-        const bool need_groups = cnt > 16u && !(pp.merge_select_min && cnt >= pp.merge_select_min && cnt <= (uint32_t)KW_SEL_PMAX);
-        if (need_groups) atomicOr(&tot->fallback, 1u);
+        if (kw_policy_needs_merge_groups(cnt, pp.merge_select_min)) atomicOr(&tot->fallback, 1u);      // the two-level merge groups are the host planner's
     }
     uint32_t c0 = tab == 0 ? cnt : 0, c1 = tab == 1 ? cnt : 0;
     unsigned long long b0 = (live && tab == 0 && cnt) ? nb : 0, b1 = (live && tab == 1 && cnt) ? nb : 0;

@@ -10,6 +10,8 @@
 #include <cmath>
 #include "kw_kernels.hip.h"
 #include "kw_plan.hip.h"
+#include "kw_plan_digest.h"
+#include "kw_translate.h"
 
 using namespace tsgpu;
 
@@ -373,6 +375,7 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "kw_candidates_rank_fold")) { ctx->kw_candidates_rank_fold = value != 0; return ok(); }
     if (!strcmp(name, "kw_mf_pipelined")) { ctx->kw_mf_pipelined = value != 0; return ok(); }
     if (!strcmp(name, "kw_count_touched")) { ctx->kw_count_touched = value != 0; return ok(); }
+    if (!strcmp(name, "kw_plan_digest")) { ctx->kw_plan_digest = value != 0; return ok(); }
     if (!strcmp(name, "kw_find_dir_tile")) { ctx->kw_find_dir_tile = value != 0; return ok(); }
     if (!strcmp(name, "kw_find_dir_span_pct")) { ctx->kw_find_dir_span_pct = std::min<int64_t>(std::max<int64_t>(value, 1), 1 << 20); return ok(); }
     if (!strcmp(name, "kw_iddir_min_ids")) { ctx->kw_iddir_min_ids = value < 0 ? 0 : value; ctx->commit_force_full = true; return ok(); }
@@ -492,6 +495,8 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "kw_book_us")) { *out = ctx->kw_book_us.load(); return ok(); }
     if (!strcmp(name, "kw_device_plans")) { *out = ctx->kw_device_plans.load(); return ok(); }                     // batches planned on the device / sent back to the host planner
     if (!strcmp(name, "kw_device_plan_fallbacks")) { *out = ctx->kw_device_plan_fallbacks.load(); return ok(); }
+    if (!strcmp(name, "kw_last_plan_cut_digest")) { *out = ctx->kw_last_plan_cut_digest; return ok(); }                 // the last keyword batch run under option kw_plan_digest (kw_plan_digest.h)
+    if (!strcmp(name, "kw_last_plan_layout_digest")) { *out = ctx->kw_last_plan_layout_digest; return ok(); }
     if (!strcmp(name, "sort_keys_live")) { *out = ctx->sort_keys_live.load(); return ok(); }                         // tsgpu_sort_key_create_eval minus _destroy
     // the last keyword batch run under option kw_count_touched: work items that took the find kernel's directory mode, pairs of driver blocks searched,
     // of them through a directory tile, and pairs of directory-mode items too wide for the tile (probed per candidate)
@@ -522,9 +527,8 @@ int tsgpu_keep_result_ids(tsgpu_ctx* ctx, int keep) {
 namespace {
 struct Plan {
     std::vector<KwQueryDev> q;
-    std::vector<KwWorkItem> work_small, work_big;   // TMAX 3 / TMAX 10 kernels
-    std::vector<KwWorkItem> work_mf_small, work_mf_big;   // multi-field kernels, TMAX 3 / TMAX 10
-    std::vector<KwWorkItem> work_wild;                    // wildcard scans
+    std::vector<KwWorkItem> work;                         // ONE work table, five kernel tables back to back: single-field TMAX 3 / TMAX 10, multi-field TMAX 3 / TMAX 10, wildcard scans
+    size_t n_tab[5] = {0, 0, 0, 0, 0};                    // ... and their sizes
     std::vector<KwQueryMF> mf;
     std::vector<KwMergeGroup> groups;                     // first level of the two-level merge (queries with many work items)
     std::vector<uint32_t> ordered_count_q;                // multi-field queries with filter AND excluded ids (kw_mf_ordered_count_kernel)
@@ -551,339 +555,273 @@ static uint32_t resolve_topster_size(const tsgpu_ctx* ctx, const tsgpu_kw_query&
     return std::max<uint32_t>(k, 1);
 }
 
-static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query* queries, uint32_t n_queries, Plan& P, bool keep_ids, bool wildcard, const KwVFlat* vflat = nullptr,
-                      const uint16_t* present_elsewhere = nullptr) {
-    // driver blocks per work item: fixed by the option, or (0 = auto) sized so that the batch yields a few thousand work
-    // items (>= 3 per resident workgroup slot) without fragmenting queries into more partial top-K lists than needed
-    uint32_t KW_CHUNK_BLOCKS = ctx->kw_chunk_blocks;
-    std::vector<uint32_t> handle_cache;      // single-field queries: list handle per token (KW_NONE - 1 = absent), looked up once
-    std::vector<uint8_t> cached(n_queries, 0);
-    if (KW_CHUNK_BLOCKS == 0) {
-        handle_cache.resize((size_t)n_queries * TSGPU_MAX_QUERY_TOKENS);
-        uint64_t total_blocks = 0;
-        for (uint32_t i = 0; i < n_queries; i++) {
-            const tsgpu_kw_query& in = queries[i];
-            if (in.n_tokens == 0 || in.n_tokens > TSGPU_MAX_QUERY_TOKENS || in.n_fields == 0 || in.n_fields > (uint32_t)KW_MAX_FIELDS) continue;
-            if (in.n_fields != 1) {
-                // several query_by fields: the driver is the token with the fewest postings over all fields, one group of work items per field list
-                // of it — its blocks enter the chunk rule, too (before, such batches were always cut with the minimum chunk: 2 000 two-field queries on
-                // 10M documents = 101 000 work items of 16 blocks)
-                uint64_t best_ids = ~0ull; uint32_t best_blocks = 0;
-                for (uint32_t t = 0; t < in.n_tokens; t++) {
-                    uint64_t ids = 0; uint32_t blocks = 0; bool found = false;
-                    for (uint32_t f = 0; f < in.n_fields; f++) {
-                        const uint32_t h = snap.find_handle(in.field_ids[f], in.term_ids[t]);
-                        if (h == 0xFFFFFFFFu) continue;
-                        found = true; ids += snap.h_lists[h].n_ids; blocks += snap.h_lists[h].n_blocks;
-                    }
-                    if (found && ids < best_ids) { best_ids = ids; best_blocks = blocks; }
-                }
-                total_blocks += best_blocks / 4;        // (a multi-field driver block costs ~4x a single-field one — two tile merges, wider records — so these batches are
-                                                        //  cut finer; measured, 2 000 two-field queries on 10M documents: 64-block items 20.4 ms, 16 -> 23.2, 256 -> 24.4)
-                continue;
-            }
-            uint32_t best = 0xFFFFFFFFu;
-            for (uint32_t t = 0; t < in.n_tokens; t++) {
-                const uint32_t h = snap.find_handle(in.field_ids[0], in.term_ids[t]);
-                handle_cache[(size_t)i * TSGPU_MAX_QUERY_TOKENS + t] = h != 0xFFFFFFFFu ? h : KW_NONE - 1;     // remembered for the main pass
-                if (h != 0xFFFFFFFFu) best = std::min(best, snap.h_lists[h].n_blocks);
-            }
-            cached[i] = 1;
-            if (best != 0xFFFFFFFFu) total_blocks += best;
-        }
-        uint64_t c = total_blocks / 3000;
-        KW_CHUNK_BLOCKS = 16;
-        while (KW_CHUNK_BLOCKS < (uint32_t)KW_MAX_CHUNK && KW_CHUNK_BLOCKS * 2 <= c) KW_CHUNK_BLOCKS *= 2;
-        // a small batch is as slow as its longest work item, and with the selecting merge (kw_select_partials) the merge no longer grows
-        // with the number of partial lists: cut finer (measured on 10M docs: 16 queries 0.256 -> 0.223 ms, 64 queries 0.330 -> 0.305 ms;
-        // from 256 queries on the chip is full and coarser items win again)
-        if (ctx->kw_merge_select_min && n_queries <= 128) KW_CHUNK_BLOCKS = 8;
+// ---- the host planner: plan_batch() below runs these phases in order ----
+namespace {
+// cuts a list of n_blocks driver blocks into work items of `chunk` blocks and registers them as the next items of one query (query_word: its index, with
+// the driver field of a multi-field query in the top bits); ids_base: where the list's id segment starts inside the query's
+void emit_items(std::vector<KwWorkItem>& work, uint32_t& q_begin, uint32_t& q_cnt, uint32_t query_word, uint32_t n_blocks, uint32_t chunk, uint32_t ids_base) {
+    for (uint32_t b = 0; b < n_blocks; b += chunk) {
+        if (q_cnt++ == 0) q_begin = (uint32_t)work.size();
+        work.push_back({query_word, b, std::min(n_blocks, b + chunk), ids_base + b * BLOCK_IDS});
     }
-    static const bool plan_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
-    const uint64_t tp0 = now_us();
-    P.q.resize(n_queries);
-    P.status.assign(n_queries, TSGPU_OK);
-    P.cutoff.assign(n_queries, 0);
-    const uint64_t now = now_us();
-    std::vector<uint32_t> q_begin(n_queries, 0), q_cnt(n_queries, 0);
-    std::vector<double> item_cost(n_queries, 0.0);
-    // The per-query part of the plan (handles, work items, id arenas) is independent per query: big batches are planned in slices on
-    // the context's parked host threads, every slice into its own accumulator; the slices are then concatenated in query order and the
-    // offsets a query holds into the shared arenas shifted by its slice's base (0.5 ms -> 0.1 ms of a 9 ms step at 10 000 queries).
-    struct PlanAcc {
-        std::vector<uint32_t> aux, ordered_count_q; std::vector<KwQueryMF> mf; std::vector<KwWorkItem> flat_work;
-        uint64_t fbits_words = 0, ids_total = 0, list_bytes = 0;
-        uint32_t max_k = 0;
-        bool any_deadline = false, any_s2 = false, any_aux = false, any_array = false;
-        uint32_t mf_max_fields = 0;
+}
+
+// The slices [bound(k), bound(k + 1)) a batch's queries are planned in, on n_thr threads: this one and the context's parked host threads. for_query_slices
+// hands them out dynamically (four per thread is the callers' choice: a parked thread that wakes late still finds work, the caller never idles).
+struct QuerySlices {
+    uint32_t n_queries, n_thr, n_parts;
+    uint32_t bound(uint32_t k) const { return (uint32_t)((uint64_t)n_queries * k / n_parts); }
+};
+void for_query_slices(tsgpu_ctx* ctx, const QuerySlices& sl, const std::function<void(uint32_t, uint32_t, uint32_t)>& fn) {
+    if (sl.n_thr <= 1) { for (uint32_t k = 0; k < sl.n_parts; k++) fn(k, sl.bound(k), sl.bound(k + 1)); return; }
+    std::atomic<uint32_t> next{0};
+    std::atomic<int> oom{0};
+    const std::function<void()> job = [&]() {
+        try { for (;;) { const uint32_t k = next.fetch_add(1); if (k >= sl.n_parts) break; fn(k, sl.bound(k), sl.bound(k + 1)); } } catch (const std::bad_alloc&) { oom = 1; }
     };
-    auto plan_range = [&](uint32_t lo, uint32_t hi, PlanAcc& A) {
-        A.flat_work.reserve((size_t)(hi - lo) * 4);
-        for (uint32_t i = lo; i < hi; i++) {
-            const tsgpu_kw_query& in = queries[i];
-            KwQueryDev& q = P.q[i];
-            memset(&q, 0, sizeof q);
-            q.k = 1;
-            auto unsupported = [&](const char*) { P.status[i] = TSGPU_ERR_UNSUPPORTED; };
-            if (!wildcard && (in.n_tokens == 0 || in.n_tokens > TSGPU_MAX_QUERY_TOKENS)) { unsupported("tokens"); continue; }
-            if (!wildcard && (in.n_fields == 0 || in.n_fields > (uint32_t)KW_MAX_FIELDS)) { unsupported("fields"); continue; }
-            if (!wildcard) {
-                int bad = 0;
-                for (uint32_t f = 0; f < in.n_fields && !bad; f++) {
-                    if (snap.field_is_array.find(in.field_ids[f]) == snap.field_is_array.end()) bad = TSGPU_ERR_NOT_FOUND;
-                }
-                if (bad) { P.status[i] = bad; continue; }
-            }
-            // several fields, or a string[] field: the general kernel (per-candidate probes, per-field scoring incl. the array readers);
-            // the block-merge kernel stays free of the array code (it costs 2x the registers)
-            bool multi = !wildcard && in.n_fields > 1;
-            if (!wildcard && !multi && snap.field_is_array.at(in.field_ids[0])) multi = true;
-            // dropped tokens (drop_tokens passes): probed and scored per candidate, never required -> the general kernel
-            if (!wildcard && in.n_dropped != 0) {
-                if (in.n_dropped > TSGPU_MAX_DROPPED_TOKENS || in.n_tokens + in.n_dropped > TSGPU_MAX_QUERY_TOKENS) { unsupported("dropped tokens"); continue; }
-                multi = true;
-            }
-            // filter ids with several query_by fields: num_keyword_matches has an order-free form only without exclusions (kw_score_stage)
-            // filter ids AND excluded ids with several query_by fields: num_keyword_matches needs the intersection in id order — counted by
-            // kw_mf_ordered_count_kernel from the find kernel's hit records, i.e. in the two-kernel form only (checked after the tables are laid out)
-            const bool ordered_count = multi && in.n_filter != 0 && in.n_excluded != 0;
-            if (ordered_count && !ctx->kw_two_kernels) { unsupported("filter ids AND excluded ids with several query_by fields need the two-kernel form"); continue; }
-            if (in.n_sort > TSGPU_MAX_SORT_KEYS) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-            if (in.n_filter != 0 && !in.filter_ids) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-            if (in.match_type > TSGPU_SUM_SCORE) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-            uint64_t sort_bytes_per_id = 0;                             // what the sort slots read per ranked document (list_bytes)
-            if (const int sort_rc = check_sort_slots(ctx, in.sort, in.n_sort, vflat != nullptr, vflat != nullptr, &sort_bytes_per_id)) { P.status[i] = sort_rc; continue; }   // vector_distance belongs to the vector/hybrid entry points
-            const uint32_t k = vflat ? std::max<uint32_t>(in.topster_size, 1) : resolve_topster_size(ctx, in);     // (the vector branch resolved it against ITS filter / row count)
-            if (k > TSGPU_MAX_TOPK) { unsupported("topster_size"); continue; }
-            if (in.deadline_us != 0 && now > in.deadline_us) { P.status[i] = TSGPU_ERR_DEADLINE; P.cutoff[i] = 1; continue; }
-            if (in.deadline_us != 0) { q.deadline_rem_us = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(in.deadline_us - now, 1), 0xFFFFFFFFull); A.any_deadline = true; }
+    ctx->host_pool.run(job, (int)sl.n_thr - 1);
+    if (oom) throw std::bad_alloc();
+}
 
-            if (wildcard) {
-                // Index::search_wildcard (src/index.cpp:6616-6818): rank every filter id (every seq_id without a filter) by its sort keys
-                q.mf_index = KW_NONE;
-                q.n_sort = (uint8_t)in.n_sort;
-                for (uint32_t s = 0; s < in.n_sort; s++) { q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column; }
-                q.k = k;
-                A.max_k = std::max(A.max_k, k);
-                q.n_excl = in.n_excluded;
-                q.n_filt = in.n_filter;
-                if (vflat) {
-                    // flat vector branch: query i ranks ITS row of the distance matrix (aligned with the filter ids); the queries of a call share
-                    // one filter (same host array): uploaded once per planning slice
-                    if (in.n_excluded || !in.n_filter) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-                    q.vdist = (uint64_t)(uintptr_t)(vflat->dist_dev + (size_t)i * vflat->stride);
-                    q.vdist_thr = vflat->threshold; q.vdist_abs = vflat->abs ? 1 : 0;
-                }
-                if (vflat && i > lo && P.status[i - 1] == TSGPU_OK && queries[i - 1].filter_ids == in.filter_ids && queries[i - 1].n_filter == in.n_filter) q.aux_off = P.q[i - 1].aux_off;
-                else {
-                    q.aux_off = (uint32_t)A.aux.size();
-                    if (in.n_excluded) {
-                        if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; continue; }
-                        A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
-                    }
-                    if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);
-                }
-                uint32_t n_ids = in.n_filter ? in.n_filter : ctx->num_docs;
-                if (!vflat && ctx->doc_range_set) {
-                    // a doc-range shard ranks the ids it OWNS: the filter ids inside [lo, hi) (a sub-array: they ascend), or lo .. hi - 1
-                    const uint32_t lo_id = ctx->doc_range_lo, hi_id = std::min(ctx->doc_range_hi, ctx->num_docs);
-                    if (in.n_filter) {
-                        const uint32_t* fb = in.filter_ids;
-                        const uint32_t a = (uint32_t)(std::lower_bound(fb, fb + in.n_filter, lo_id) - fb), b = (uint32_t)(std::lower_bound(fb, fb + in.n_filter, hi_id) - fb);
-                        A.aux.resize(A.aux.size() - in.n_filter);                       // (the filter ids were appended last: keep the sub-array)
-                        A.aux.insert(A.aux.end(), fb + a, fb + b);
-                        q.n_filt = b - a;
-                        n_ids = b - a;
-                    } else { n_ids = hi_id > lo_id ? hi_id - lo_id : 0; q.wild_base = lo_id; }
-                }
-                q.wild_n_ids = n_ids;
-                if (n_ids == 0) continue;                                               // (nothing of this query on this shard: zero hits, status 0)
-                A.list_bytes += 4ull * in.n_filter + sort_bytes_per_id * n_ids;      // the id array + one column value (a key byte, the key's lists) per id and key slot
-                q.ids_out_off = A.ids_total;
-                const uint32_t n_blocks = (n_ids + BLOCK_IDS - 1) / BLOCK_IDS;
-                if (keep_ids) A.ids_total += (uint64_t)n_blocks * BLOCK_IDS;
-                const uint32_t WCHUNK = 64;                                     // 16K ids per work item
-                for (uint32_t b = 0; b < n_blocks; b += WCHUNK) {
-                    KwWorkItem w;
-                    w.query = i; w.blk_begin = b; w.blk_end = std::min(n_blocks, b + WCHUNK); w.ids_out_off = b * BLOCK_IDS;
-                    { if (q_cnt[i] == 0) q_begin[i] = (uint32_t)A.flat_work.size(); A.flat_work.push_back(w); q_cnt[i]++; }
-                }
-                continue;
-            }
+// The per-query part of the plan (handles, work items, id arenas) is independent per query: big batches are planned in slices, every slice into its own
+// accumulator; the slices are then concatenated in query order and the offsets a query holds into the shared arenas shifted by its slice's base
+// (0.5 ms -> 0.1 ms of a 9 ms step at 10 000 queries).
+struct PlanAcc {
+    std::vector<uint32_t> aux, ordered_count_q; std::vector<KwQueryMF> mf; std::vector<KwWorkItem> flat_work;
+    uint64_t fbits_words = 0, ids_total = 0, list_bytes = 0;
+    uint32_t max_k = 0;
+    bool any_deadline = false, any_s2 = false, any_aux = false, any_array = false;
+    uint32_t mf_max_fields = 0;
+};
+// what the cut needs of a translated query: every token is resolved ONCE, by translate(); the batch chunk is known only after all of them
+struct QueryCut {
+    enum Shape : uint8_t { NONE, WILDCARD, MULTI_FIELD, SINGLE_FIELD } shape = NONE;
+    uint32_t driver_blocks = 0;                   // wildcard: blocks of ids to scan; single field: the driver list's
+    uint32_t n_lists = 0, len_driver = 0, len_second = 0;      // single field: what the launch-order cost reads
+    uint32_t chunk_blocks = 0;                    // what the query adds to the batch chunk's input (kw_policy_batch_chunk)
+};
+struct QueryTokens { uint32_t nl = 0; uint32_t len_of[KW_MAX_TOKENS]; KwQueryMF mfq; };
 
-            q.n_query_tokens = in.n_tokens;
-            q.mf_index = KW_NONE;
-            uint32_t nl = 0;
-            uint32_t len_of[KW_MAX_TOKENS];
-            KwQueryMF mfq;
-            if (multi) memset(&mfq, 0xFF, sizeof mfq);                // (only read by the multi-field form)
-            bool empty_here = false;
-            for (uint32_t t = 0; t < in.n_tokens; t++) {
-                // one or_iterator per token = the union of its lists over the fields; a token found in no field is skipped (src/index.cpp:5651-5655)
-                uint64_t tot = 0;
-                bool found = false;
-                for (uint32_t f = 0; f < in.n_fields; f++) {
-                    uint32_t handle;
-                    if (cached[i]) {                     // (n_fields == 1)
-                        handle = handle_cache[(size_t)i * TSGPU_MAX_QUERY_TOKENS + t];
-                        if (handle == KW_NONE - 1) continue;
-                    } else {
-                        handle = snap.find_handle(in.field_ids[f], in.term_ids[t]);
-                        if (handle == 0xFFFFFFFFu) continue;
-                    }
-                    if (!found) q.list[nl] = handle;
-                    found = true;
-                    mfq.list[nl][f] = handle;
-                    tot += snap.h_lists[handle].n_ids;
-                    A.list_bytes += 4ull * snap.h_lists[handle].n_ids;
-                }
-                if (!found) { if (present_elsewhere && ((present_elsewhere[i] >> t) & 1u)) empty_here = true; continue; }      // (exists on another shard: an EMPTY list here)
-                len_of[nl] = (uint32_t)std::min<uint64_t>(tot, 0xFFFFFFFFull);
-                nl++;
-            }
-            if (empty_here) nl = 0;               // a required token without postings on this shard: the AND finds nothing here (zero hits below), whatever the others hold
-            q.n_required = nl;
-            for (uint32_t t = 0; t < in.n_dropped && multi; t++) {        // after the query's own tokens, in their order (:5271-5290)
-                bool found = false;
-                for (uint32_t f = 0; f < in.n_fields; f++) {
-                    const uint32_t handle = snap.find_handle(in.field_ids[f], in.dropped_term_ids[t]);
-                    if (handle == 0xFFFFFFFFu) continue;
-                    mfq.list[nl][f] = handle;
-                    found = true;
-                    A.list_bytes += 4ull * snap.h_lists[handle].n_ids;
-                }
-                if (!found) continue;                                     // an or_iterator without lists: skip_to() is false for every document
-                len_of[nl] = 0xFFFFFFFFu;
-                nl++;
-            }
-            q.n_lists = nl;
-            q.match_type = in.match_type;
-            q.prio_exact = in.prioritize_exact_match ? 1 : 0;
-            q.prio_pos = in.prioritize_token_position ? 1 : 0;
-            q.prio_nfields = in.prioritize_num_matching_fields ? 1 : 0;
-            q.total_cost = in.total_cost;
-            q.weight = in.field_weights[0];
-            q.syn_orig_num_tokens = (int8_t)((int)in.syn_orig_num_tokens_p1 - 1);
-            q.orig_num_tokens = in.orig_num_tokens; q.is_synonym = in.is_synonym_query ? 1 : 0; q.demote_synonym = in.demote_synonym_match ? 1 : 0;
-            q.n_sort = (uint8_t)in.n_sort;
-            if (in.n_sort > 2) A.any_s2 = true;
-            for (uint32_t s = 0; s < in.n_sort; s++) { q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column; }
-            q.k = k;
-            A.max_k = std::max(A.max_k, k);
+struct BatchPlanner {
+    tsgpu_ctx* ctx; const Snapshot& snap; const tsgpu_kw_query* queries; uint32_t n_queries; Plan& P; bool keep_ids, wildcard; const KwVFlat* vflat; const uint16_t* present_elsewhere;
+    uint64_t now;
+    std::vector<QueryCut> cut; std::vector<uint32_t> q_begin, q_cnt; std::vector<double> item_cost;
+    std::vector<KwWorkItem> flat_work;                       // every query's items, contiguous, in query order
+
+    // one or_iterator per token that exists in some field (kw_translate.h), in query order; returns the bytes of its lists
+    uint64_t add_token(uint32_t i, QueryTokens& T, const KwTokenLists& tl, uint32_t len) {
+        P.q[i].list[T.nl] = tl.first;
+        for (uint32_t f = 0; f < (uint32_t)KW_MAX_FIELDS; f++) if (tl.handle[f] != KW_NONE) T.mfq.list[T.nl][f] = tl.handle[f];
+        T.len_of[T.nl++] = len;
+        return 4ull * tl.ids;
+    }
+
+    // Index::search_wildcard (src/index.cpp:6616-6818): rank every filter id (every seq_id without a filter) by its sort keys
+    void wildcard_query(uint32_t i, uint32_t lo, uint32_t k, uint64_t sort_bytes_per_id, PlanAcc& A) {
+        const tsgpu_kw_query& in = queries[i];
+        KwQueryDev& q = P.q[i];
+        q.mf_index = KW_NONE;
+        kw_fill_sort_slots(in, q);
+        q.k = k;
+        A.max_k = std::max(A.max_k, k);
+        q.n_excl = in.n_excluded;
+        q.n_filt = in.n_filter;
+        if (vflat) {
+            // flat vector branch: query i ranks ITS row of the distance matrix (aligned with the filter ids); the queries of a call share
+            // one filter (same host array): uploaded once per planning slice
+            if (in.n_excluded || !in.n_filter) { P.status[i] = TSGPU_ERR_INVALID; return; }
+            q.vdist = (uint64_t)(uintptr_t)(vflat->dist_dev + (size_t)i * vflat->stride);
+            q.vdist_thr = vflat->threshold; q.vdist_abs = vflat->abs ? 1 : 0;
+        }
+        if (vflat && i > lo && P.status[i - 1] == TSGPU_OK && queries[i - 1].filter_ids == in.filter_ids && queries[i - 1].n_filter == in.n_filter) q.aux_off = P.q[i - 1].aux_off;
+        else {
             q.aux_off = (uint32_t)A.aux.size();
-            q.n_excl = in.n_excluded;
-            q.n_filt = in.n_filter;
-            if (in.n_excluded || in.n_filter) A.any_aux = true;
-            for (uint32_t s = 0; s < in.n_sort; s++) if (in.sort[s].kind >= TSGPU_SORT_EVAL) A.any_aux = true;      // (the PLAIN score kernels carry no sort-key code)
             if (in.n_excluded) {
-                if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; continue; }
+                if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; return; }
                 A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
             }
-            if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);   // sorted ascending, unique (filter_result_t::docs)
-            if (q.n_required == 0) continue;   // no token in the index: zero hits (intersect case 0, or_iterator.h:67-68)
-            if (multi) {
-                // driver = the token with the fewest postings over all fields; one group of work items per field list of it
-                uint32_t td = 0;
-                for (uint32_t t = 1; t < q.n_required; t++) if (len_of[t] < len_of[td]) td = t;
-                mfq.n_fields = in.n_fields;
-                A.mf_max_fields = std::max(A.mf_max_fields, (uint32_t)in.n_fields);
-                mfq.driver_token = td;
-                mfq.second_token = KW_NONE;             // the required token with the next fewest postings: merged block-wise by the find kernel
-                for (uint32_t t = 0; t < q.n_required; t++) if (t != td && (mfq.second_token == KW_NONE || len_of[t] < len_of[mfq.second_token])) mfq.second_token = t;
-                for (uint32_t f = 0; f < (uint32_t)KW_MAX_FIELDS; f++) { mfq.is_array[f] = f < in.n_fields && snap.field_is_array.at(in.field_ids[f]) ? 1 : 0; if (mfq.is_array[f]) A.any_array = true; }
-                for (uint32_t f = 0; f < (uint32_t)KW_MAX_FIELDS; f++) mfq.weight[f] = f < in.n_fields ? in.field_weights[f] : 0;
-                if (k + KW_THREADS > 1024) { unsupported("topster_size with several query_by fields"); continue; }
-                q.mf_index = (uint32_t)A.mf.size();
-                A.mf.push_back(mfq);
-                if (ordered_count) A.ordered_count_q.push_back(i);
-                if (in.n_filter) { q.fbits_off = A.fbits_words; A.fbits_words += ((uint64_t)in.n_filter + 31) / 32; }
-                q.ids_out_off = A.ids_total;
-                uint64_t seg = 0;
-                for (uint32_t f = 0; f < in.n_fields; f++) {
-                    if (mfq.list[td][f] == KW_NONE) continue;
-                    const ListDesc& dF = snap.h_lists[mfq.list[td][f]];
-                    for (uint32_t b = 0; b < dF.n_blocks; b += KW_CHUNK_BLOCKS) {
-                        KwWorkItem w;
-                        w.query = i | (f << 28);
-                        w.blk_begin = b;
-                        w.blk_end = std::min(dF.n_blocks, b + KW_CHUNK_BLOCKS);
-                        w.ids_out_off = (uint32_t)seg;
-                        seg += (uint64_t)(w.blk_end - w.blk_begin) * BLOCK_IDS;
-                        { if (q_cnt[i] == 0) q_begin[i] = (uint32_t)A.flat_work.size(); A.flat_work.push_back(w); q_cnt[i]++; }
-                    }
-                }
-                if (keep_ids) A.ids_total += seg;
-                continue;
-            }
-            // probe order: ascending list length, stable
-            uint8_t ord[KW_MAX_TOKENS];
-            for (uint32_t t = 0; t < nl; t++) ord[t] = (uint8_t)t;
-            std::stable_sort(ord, ord + nl, [&](uint8_t a, uint8_t b) { return len_of[a] < len_of[b]; });
-            for (uint32_t t = 0; t < nl; t++) q.probe_order[t] = ord[t];
-            const ListDesc& dA = snap.h_lists[q.list[ord[0]]];
-            q.ids_out_off = A.ids_total;
-            if (keep_ids) A.ids_total += (uint64_t)dA.n_blocks * BLOCK_IDS;
-            // at most 8..64 partial top-K lists per query: kw_merge_kernel folds a query's partials one after the other, and a small
-            // batch (auto chunk 16) would otherwise cut a long driver list into hundreds of work items
-            // (small batches: a few thousand work items fill the chip, more only lengthen the per-query merge chain; measured on the
-            // 10M-doc collection: 100 queries 1.47 -> 1.15 ms, while a cap of 8 at 1 000+ queries unbalances the search kernel)
-            uint32_t chunk_q = KW_CHUNK_BLOCKS;
-            // small batches are as slow as their heaviest query: its longest work item (~3 us per driver block when the chip is not full)
-            // plus the chain of partial folds in kw_merge_kernel (~4.5 us each) -> the item count that balances the two, ~sqrt(blocks / 1.5)
-            uint32_t max_partials = ctx->kw_max_partials;
-            // (with the two-level merge a chain of P folds costs G + P / G, G = 8: the balance moves to ~sqrt(2.7 x blocks) items)
-            if (n_queries < 512) max_partials = std::max(max_partials, std::min<uint32_t>(384, (uint32_t)std::sqrt((double)dA.n_blocks * 2.7)));
-            if (ctx->kw_merge_select_min && n_queries <= 128) max_partials = (uint32_t)KW_SEL_PMAX;        // (the selecting merge: see the chunk rule above)
-            // ... but never longer than 256 blocks (only the batch-wide chunk of a very large batch goes beyond, up to KW_MAX_CHUNK): the batch is as slow as its longest work item (a 16K-block driver list cut in 16
-            // would run 1 000 blocks in sequence), and folding 64 sorted partials costs kw_merge_kernel ~0.3 ms
-            if (ctx->kw_chunk_blocks == 0) chunk_q = std::max(chunk_q, std::min<uint32_t>((dA.n_blocks + max_partials - 1) / max_partials, 256u));
-            {   // launch-order key: estimated cost of the query's LARGEST work item = driver blocks x (fixed cost + second-list ids per
-                // driver id); the work table is laid out heaviest first so that the long items do not start last (tail of the launch)
-                const double r = nl >= 2 ? (double)len_of[ord[1]] / (double)std::max<uint32_t>(len_of[ord[0]], 1) : 0.0;
-                // + third-list probes: every stage-1 survivor (256 |B| / N per driver block) costs a two-level global binary search
-                const double surv = nl >= 3 ? 256.0 * (double)len_of[ord[1]] / (double)std::max<uint32_t>(ctx->num_docs, 1) : 0.0;
-                item_cost[i] = (double)std::min(chunk_q, dA.n_blocks) * ((double)ctx->kw_cost_fixed + 0.1 * ctx->kw_cost_r_x10 * std::min(r, 64.0) + 0.01 * ctx->kw_cost_probe_x100 * surv);
-            }
-            for (uint32_t b = 0; b < dA.n_blocks; b += chunk_q) {
-                KwWorkItem w;
-                w.query = i;
-                w.blk_begin = b;
-                w.blk_end = std::min(dA.n_blocks, b + chunk_q);
-                w.ids_out_off = b * BLOCK_IDS;
-                { if (q_cnt[i] == 0) q_begin[i] = (uint32_t)A.flat_work.size(); A.flat_work.push_back(w); q_cnt[i]++; }
-            }
+            if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);
         }
-    };
-    std::vector<KwWorkItem> flat_work;                       // every query's items, contiguous, in query order
-    {
-        const uint32_t min_par = ctx->plan_parallel_min_queries;
-        const uint32_t min_slice = std::max<uint32_t>(8, min_par / 8);                      // (256 queries per slice at the default threshold)
-        const uint32_t n_thr = (min_par && n_queries >= min_par) ? std::min<uint32_t>((uint32_t)std::max(1, ctx->plan_threads), std::max<uint32_t>(1, n_queries / min_slice)) : 1;
-        // (four slices per thread, handed out dynamically: a parked thread that wakes late still finds work, the caller never idles)
-        const uint32_t n_parts = n_thr == 1 ? 1 : std::min<uint32_t>(4 * n_thr, std::max<uint32_t>(1, n_queries / std::max<uint32_t>(8, min_slice / 4)));
-        std::vector<PlanAcc> parts(n_parts);
-        auto bound = [&](uint32_t k) { return (uint32_t)((uint64_t)n_queries * k / n_parts); };
-        if (n_parts == 1) plan_range(0, n_queries, parts[0]);
-        else {
-            std::atomic<uint32_t> next{0};
-            std::atomic<int> oom{0};
-            const std::function<void()> job = [&]() {
-                try { for (;;) { const uint32_t k = next.fetch_add(1); if (k >= n_parts) break; plan_range(bound(k), bound(k + 1), parts[k]); } } catch (const std::bad_alloc&) { oom = 1; }
-            };
-            ctx->host_pool.run(job, (int)n_thr - 1);
-            if (oom) throw std::bad_alloc();
+        uint32_t n_ids = in.n_filter ? in.n_filter : ctx->num_docs;
+        if (!vflat && ctx->doc_range_set) {
+            // a doc-range shard ranks the ids it OWNS: the filter ids inside [lo, hi) (a sub-array: they ascend), or lo .. hi - 1
+            const uint32_t lo_id = ctx->doc_range_lo, hi_id = std::min(ctx->doc_range_hi, ctx->num_docs);
+            if (in.n_filter) {
+                const uint32_t* fb = in.filter_ids;
+                const uint32_t a = (uint32_t)(std::lower_bound(fb, fb + in.n_filter, lo_id) - fb), b = (uint32_t)(std::lower_bound(fb, fb + in.n_filter, hi_id) - fb);
+                A.aux.resize(A.aux.size() - in.n_filter);                       // (the filter ids were appended last: keep the sub-array)
+                A.aux.insert(A.aux.end(), fb + a, fb + b);
+                q.n_filt = b - a;
+                n_ids = b - a;
+            } else { n_ids = hi_id > lo_id ? hi_id - lo_id : 0; q.wild_base = lo_id; }
         }
-        for (uint32_t k = 0; k < n_parts; k++) {
+        q.wild_n_ids = n_ids;
+        if (n_ids == 0) return;                                                 // (nothing of this query on this shard: zero hits, status 0)
+        A.list_bytes += 4ull * in.n_filter + sort_bytes_per_id * n_ids;      // the id array + one column value (a key byte, the key's lists) per id and key slot
+        q.ids_out_off = A.ids_total;
+        cut[i].shape = QueryCut::WILDCARD;
+        cut[i].driver_blocks = (n_ids + BLOCK_IDS - 1) / BLOCK_IDS;
+        if (keep_ids) A.ids_total += (uint64_t)cut[i].driver_blocks * BLOCK_IDS;
+    }
+
+    // several query_by fields, a string[] field or dropped tokens: driver = the token with the fewest postings over all fields, one group of work items
+    // per field list of it
+    void multi_field_query(uint32_t i, uint32_t k, bool ordered_count, QueryTokens& T, PlanAcc& A) {
+        const tsgpu_kw_query& in = queries[i];
+        KwQueryDev& q = P.q[i];
+        KwQueryMF& mfq = T.mfq;
+        uint32_t td = 0;
+        for (uint32_t t = 1; t < q.n_required; t++) if (T.len_of[t] < T.len_of[td]) td = t;
+        A.mf_max_fields = std::max(A.mf_max_fields, (uint32_t)in.n_fields);
+        mfq.driver_token = td;
+        mfq.second_token = KW_NONE;             // the required token with the next fewest postings: merged block-wise by the find kernel
+        for (uint32_t t = 0; t < q.n_required; t++) if (t != td && (mfq.second_token == KW_NONE || T.len_of[t] < T.len_of[mfq.second_token])) mfq.second_token = t;
+        (void)kw_fill_fields(snap, in, mfq, &A.any_array);      // (the fields exist: translate() checked)
+        if (k + KW_THREADS > 1024) { P.status[i] = TSGPU_ERR_UNSUPPORTED; return; }      // topster_size with several query_by fields
+        q.mf_index = (uint32_t)A.mf.size();
+        A.mf.push_back(mfq);
+        if (ordered_count) A.ordered_count_q.push_back(i);
+        if (in.n_filter) { q.fbits_off = A.fbits_words; A.fbits_words += ((uint64_t)in.n_filter + 31) / 32; }
+        q.ids_out_off = A.ids_total;
+        cut[i].shape = QueryCut::MULTI_FIELD;
+        for (uint32_t f = 0; f < in.n_fields && keep_ids; f++)      // the fields' id segments, one behind the other
+            if (mfq.list[td][f] != KW_NONE) A.ids_total += (uint64_t)snap.h_lists[mfq.list[td][f]].n_blocks * BLOCK_IDS;
+    }
+
+    // one plain string field: the block-merge kernels; probe order = ascending list length, stable
+    void single_field_query(uint32_t i, const QueryTokens& T, PlanAcc& A) {
+        KwQueryDev& q = P.q[i];
+        uint8_t ord[KW_MAX_TOKENS];
+        for (uint32_t t = 0; t < T.nl; t++) ord[t] = (uint8_t)t;
+        std::stable_sort(ord, ord + T.nl, [&](uint8_t a, uint8_t b) { return T.len_of[a] < T.len_of[b]; });
+        for (uint32_t t = 0; t < T.nl; t++) q.probe_order[t] = ord[t];
+        QueryCut& c = cut[i];
+        c.shape = QueryCut::SINGLE_FIELD;
+        c.driver_blocks = snap.h_lists[q.list[ord[0]]].n_blocks;
+        c.n_lists = T.nl; c.len_driver = T.len_of[ord[0]]; c.len_second = T.nl >= 2 ? T.len_of[ord[1]] : 0;
+        q.ids_out_off = A.ids_total;
+        if (keep_ids) A.ids_total += (uint64_t)c.driver_blocks * BLOCK_IDS;
+    }
+
+    // query i -> its KwQueryDev, its share of the slice's arenas and its QueryCut: the checks (the first that fails is the query's status), the token
+    // lists, what every keyword query carries, then its shape
+    void translate(uint32_t i, uint32_t lo, PlanAcc& A) {
+        const tsgpu_kw_query& in = queries[i];
+        KwQueryDev& q = P.q[i];
+        memset(&q, 0, sizeof q);
+        q.k = 1;
+        auto refuse = [&](int status) { P.status[i] = status; };
+        if (!wildcard && !kw_token_count_ok(in)) return refuse(TSGPU_ERR_UNSUPPORTED);
+        if (!wildcard && !kw_field_count_ok(in)) return refuse(TSGPU_ERR_UNSUPPORTED);
+        QueryTokens T;
+        uint64_t token_bytes = 0;
+        bool empty_here = false;
+        if (!wildcard) {
+            // the required tokens, resolved here because EVERY query with a legal token and field count enters the batch chunk, whatever it is refused for below:
+            // one query_by field: its shortest list's blocks; several: the blocks of the token with the fewest postings over all fields, a quarter of them
+            // (a multi-field driver block costs ~4x a single-field one — two tile merges, wider records — so these batches are cut finer; measured, 2 000
+            //  two-field queries on 10M documents: 64-block items 20.4 ms, 16 -> 23.2, 256 -> 24.4; cut with the minimum chunk they were 101 000 work items)
+            memset(&T.mfq, 0xFF, sizeof T.mfq);
+            uint64_t best_ids = ~0ull; uint32_t best_blocks = 0xFFFFFFFFu;
+            for (uint32_t t = 0; t < in.n_tokens; t++) {
+                const KwTokenLists tl = kw_resolve_token(snap, in, in.term_ids[t]);
+                if (!tl.found) { if (present_elsewhere && ((present_elsewhere[i] >> t) & 1u)) empty_here = true; continue; }      // (exists on another shard: an EMPTY list here)
+                token_bytes += add_token(i, T, tl, (uint32_t)std::min<uint64_t>(tl.ids, 0xFFFFFFFFull));
+                if (in.n_fields == 1) best_blocks = std::min(best_blocks, tl.blocks);
+                else if (tl.ids < best_ids) { best_ids = tl.ids; best_blocks = tl.blocks; }
+            }
+            if (best_blocks == 0xFFFFFFFFu) best_blocks = 0;
+            cut[i].chunk_blocks = in.n_fields == 1 ? best_blocks : best_blocks / 4;
+            for (uint32_t f = 0; f < in.n_fields; f++) if (snap.field_is_array.find(in.field_ids[f]) == snap.field_is_array.end()) return refuse(TSGPU_ERR_NOT_FOUND);
+        }
+        // several fields, or a string[] field: the general kernel (per-candidate probes, per-field scoring incl. the array readers);
+        // the block-merge kernel stays free of the array code (it costs 2x the registers)
+        bool multi = !wildcard && in.n_fields > 1;
+        if (!wildcard && !multi && snap.field_is_array.at(in.field_ids[0])) multi = true;
+        // dropped tokens (drop_tokens passes): probed and scored per candidate, never required -> the general kernel
+        if (!wildcard && in.n_dropped != 0) {
+            if (!kw_dropped_count_ok(in)) return refuse(TSGPU_ERR_UNSUPPORTED);
+            multi = true;
+        }
+        // filter ids with several query_by fields: num_keyword_matches has an order-free form only without exclusions (kw_score_stage)
+        // filter ids AND excluded ids with several query_by fields: num_keyword_matches needs the intersection in id order — counted by
+        // kw_mf_ordered_count_kernel from the find kernel's hit records, i.e. in the two-kernel form only (checked after the tables are laid out)
+        const bool ordered_count = multi && in.n_filter != 0 && in.n_excluded != 0;
+        if (ordered_count && !ctx->kw_two_kernels) return refuse(TSGPU_ERR_UNSUPPORTED);
+        if (in.n_sort > TSGPU_MAX_SORT_KEYS) return refuse(TSGPU_ERR_INVALID);
+        if (in.n_filter != 0 && !in.filter_ids) return refuse(TSGPU_ERR_INVALID);
+        if (in.match_type > TSGPU_SUM_SCORE) return refuse(TSGPU_ERR_INVALID);
+        uint64_t sort_bytes_per_id = 0;                             // what the sort slots read per ranked document (list_bytes)
+        if (const int sort_rc = check_sort_slots(ctx, in.sort, in.n_sort, vflat != nullptr, vflat != nullptr, &sort_bytes_per_id)) return refuse(sort_rc);   // vector_distance belongs to the vector/hybrid entry points
+        const uint32_t k = vflat ? std::max<uint32_t>(in.topster_size, 1) : resolve_topster_size(ctx, in);     // (the vector branch resolved it against ITS filter / row count)
+        if (k > TSGPU_MAX_TOPK) return refuse(TSGPU_ERR_UNSUPPORTED);
+        if (in.deadline_us != 0 && now > in.deadline_us) { P.cutoff[i] = 1; return refuse(TSGPU_ERR_DEADLINE); }
+        if (in.deadline_us != 0) { q.deadline_rem_us = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(in.deadline_us - now, 1), 0xFFFFFFFFull); A.any_deadline = true; }
+        if (wildcard) return wildcard_query(i, lo, k, sort_bytes_per_id, A);
+
+        q.mf_index = KW_NONE;
+        if (empty_here) T.nl = 0;             // a required token without postings on this shard: the AND finds nothing here (zero hits below), whatever the others hold
+        q.n_required = T.nl;
+        for (uint32_t t = 0; t < in.n_dropped && multi; t++) {        // after the query's own tokens, in their order (:5271-5290)
+            const KwTokenLists tl = kw_resolve_token(snap, in, in.dropped_term_ids[t]);
+            if (tl.found) token_bytes += add_token(i, T, tl, 0xFFFFFFFFu);      // (an or_iterator without lists is left out: skip_to() is false for every document)
+        }
+        A.list_bytes += token_bytes;
+        q.n_lists = T.nl;
+        kw_fill_scoring(in, q);
+        kw_fill_sort_slots(in, q);
+        if (in.n_sort > 2) A.any_s2 = true;
+        q.k = k;
+        A.max_k = std::max(A.max_k, k);
+        q.aux_off = (uint32_t)A.aux.size();
+        q.n_excl = in.n_excluded;
+        q.n_filt = in.n_filter;
+        if (in.n_excluded || in.n_filter) A.any_aux = true;
+        for (uint32_t s = 0; s < in.n_sort; s++) if (in.sort[s].kind >= TSGPU_SORT_EVAL) A.any_aux = true;      // (the PLAIN score kernels carry no sort-key code)
+        if (in.n_excluded) {
+            if (!in.excluded_ids) return refuse(TSGPU_ERR_INVALID);
+            A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
+        }
+        if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);   // sorted ascending, unique (filter_result_t::docs)
+        if (q.n_required == 0) return;     // no token in the index: zero hits (intersect case 0, or_iterator.h:67-68)
+        if (multi) multi_field_query(i, k, ordered_count, T, A);
+        else single_field_query(i, T, A);
+    }
+
+    // the cut of query i's driver list(s) into work items (kw_plan_policy.h) and, for the block-merge kernels, its launch-order cost
+    void cut_items(uint32_t i, uint32_t batch_chunk, PlanAcc& A) {
+        const QueryCut& c = cut[i];
+        if (P.status[i] != TSGPU_OK || c.shape == QueryCut::NONE) return;
+        if (c.shape == QueryCut::WILDCARD) return emit_items(A.flat_work, q_begin[i], q_cnt[i], i, c.driver_blocks, KW_POLICY_WILDCARD_CHUNK, 0);
+        if (c.shape == QueryCut::MULTI_FIELD) {
+            const KwQueryMF& mfq = A.mf[P.q[i].mf_index];
+            uint64_t seg = 0;
+            for (uint32_t f = 0; f < mfq.n_fields; f++) {
+                if (mfq.list[mfq.driver_token][f] == KW_NONE) continue;
+                const uint32_t n_blocks = snap.h_lists[mfq.list[mfq.driver_token][f]].n_blocks;
+                emit_items(A.flat_work, q_begin[i], q_cnt[i], i | (f << 28), n_blocks, batch_chunk, (uint32_t)seg);
+                seg += (uint64_t)n_blocks * BLOCK_IDS;
+            }
+            return;
+        }
+        const uint32_t chunk_q = kw_policy_query_chunk(batch_chunk, ctx->kw_chunk_blocks == 0, c.driver_blocks,
+                                                       kw_policy_max_partials(ctx->kw_max_partials, c.driver_blocks, n_queries, ctx->kw_merge_select_min));
+        item_cost[i] = kw_policy_item_cost<double>(chunk_q, c.driver_blocks, c.n_lists, c.len_driver, c.len_second, ctx->num_docs, (double)ctx->kw_cost_fixed,
+                                                   0.1 * ctx->kw_cost_r_x10, 0.01 * ctx->kw_cost_probe_x100);
+        emit_items(A.flat_work, q_begin[i], q_cnt[i], i, c.driver_blocks, chunk_q, 0);
+    }
+
+    // the slices' arenas one behind the other, every query's offsets shifted by its slice's bases
+    void concatenate(std::vector<PlanAcc>& parts, const QuerySlices& sl) {
+        for (uint32_t k = 0; k < sl.n_parts; k++) {
             PlanAcc& A = parts[k];
             const uint32_t aux_base = (uint32_t)P.aux.size(), mf_base = (uint32_t)P.mf.size(), work_base = (uint32_t)flat_work.size();
             const uint64_t ids_base = P.ids_total, fbits_base = P.fbits_words;
-            if (k) {
-                for (uint32_t i = bound(k); i < bound(k + 1); i++) {
-                    KwQueryDev& q = P.q[i];
-                    q.aux_off += aux_base; q.ids_out_off += ids_base; q.fbits_off += fbits_base;
-                    if (q.mf_index != KW_NONE && P.status[i] == TSGPU_OK && !q.wild_n_ids) q.mf_index += mf_base;
-                    q_begin[i] += work_base;
-                }
+            for (uint32_t i = sl.bound(k); k && i < sl.bound(k + 1); i++) {
+                KwQueryDev& q = P.q[i];
+                q.aux_off += aux_base; q.ids_out_off += ids_base; q.fbits_off += fbits_base;
+                if (q.mf_index != KW_NONE && P.status[i] == TSGPU_OK && !q.wild_n_ids) q.mf_index += mf_base;
+                q_begin[i] += work_base;
             }
             if (k == 0) { P.aux.swap(A.aux); P.mf.swap(A.mf); flat_work.swap(A.flat_work); }
             else {
@@ -897,22 +835,20 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             P.any_deadline = P.any_deadline || A.any_deadline; P.any_s2 = P.any_s2 || A.any_s2; P.any_aux = P.any_aux || A.any_aux; P.any_array = P.any_array || A.any_array; P.mf_max_fields = std::max(P.mf_max_fields, A.mf_max_fields);
         }
     }
-    // work tables: one launch per kernel flavour (single-field T<=3, single-field generic, multi-field T<=3, multi-field generic);
-    // a query's items stay contiguous and first_work indexes the concatenation of the four tables
-    const uint64_t tp1 = now_us();
-    std::vector<uint32_t> by_cost(n_queries);
-    for (uint32_t i = 0; i < n_queries; i++) by_cost[i] = i;
-    if (ctx->kw_sort_work) {
-        // descending cost, ties in query order: LSD radix sort of the float bits (costs are non-negative, so the bits order like the
-        // values), two stable counting passes of 16 bits (std::sort of 10 000 keys was 0.33 ms of a 0.95 ms plan; a coarser one-pass
-        // bucket order measurably lengthened the find kernel's tail)
+
+    // the queries by descending cost, ties in query order (option kw_sort_work; else query order)
+    std::vector<uint32_t> cost_order() const {
+        std::vector<uint32_t> by_cost(n_queries);
+        for (uint32_t i = 0; i < n_queries; i++) by_cost[i] = i;
+        if (!ctx->kw_sort_work) return by_cost;
+        // LSD radix sort of the float bits (costs are non-negative, so the bits order like the values), two stable counting passes of 16 bits (std::sort of
+        // 10 000 keys was 0.33 ms of a 0.95 ms plan; a coarser one-pass bucket order measurably lengthened the find kernel's tail)
         // (the two 65 536-entry histograms are a FIXED ~30 us: a small round — the 1-query calling convention — sorts by comparison)
         std::vector<uint32_t> key(n_queries);
         for (uint32_t i = 0; i < n_queries; i++) { const float c = (float)item_cost[i]; uint32_t bits; memcpy(&bits, &c, 4); key[i] = 0xFFFFFFFFu - bits; }
-        const bool radix = n_queries >= 2048;
-        if (!radix && n_queries > 1) std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-        std::vector<uint32_t> tmp(radix ? n_queries : 0), hist(radix ? 65537 : 0);
-        for (int pass = 0; radix && pass < 2; pass++) {
+        if (n_queries < 2048) { std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; }); return by_cost; }
+        std::vector<uint32_t> tmp(n_queries), hist(65537);
+        for (int pass = 0; pass < 2; pass++) {
             const int sh = pass * 16;
             std::fill(hist.begin(), hist.end(), 0u);
             for (uint32_t i = 0; i < n_queries; i++) hist[((key[by_cost[i]] >> sh) & 0xFFFFu) + 1]++;
@@ -920,39 +856,73 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
             for (uint32_t i = 0; i < n_queries; i++) { const uint32_t q = by_cost[i]; tmp[hist[(key[q] >> sh) & 0xFFFFu]++] = q; }
             by_cost.swap(tmp);
         }
+        return by_cost;
     }
-    const uint64_t tp2 = now_us();
-    {
-        std::vector<KwWorkItem>* tabs[5] = {&P.work_small, &P.work_big, &P.work_mf_small, &P.work_mf_big, &P.work_wild};
+
+    // work tables: one launch per kernel flavour (single-field T<=3, single-field generic, multi-field T<=3, multi-field generic, wildcard); a query's
+    // items stay contiguous and first_work indexes the one table that holds the five back to back, heaviest query first inside each
+    void layout_tables(const std::vector<uint32_t>& by_cost) {
         auto flavour_of = [&](uint32_t i) { return P.q[i].wild_n_ids ? 4 : (P.q[i].mf_index != KW_NONE ? 2 : 0) + (P.q[i].n_lists <= 3 ? 0 : 1); };
-        size_t total[5] = {0, 0, 0, 0, 0}, base[5];
-        for (uint32_t i = 0; i < n_queries; i++) if (q_cnt[i]) total[flavour_of(i)] += q_cnt[i];
-        size_t acc = 0;
-        for (int k = 0; k < 5; k++) { base[k] = acc; acc += total[k]; tabs[k]->reserve(total[k]); }
-        for (uint32_t oi = 0; oi < n_queries; oi++) {              // heaviest first inside every table
-            const uint32_t i = by_cost[oi];
+        size_t at[5], acc = 0;
+        for (uint32_t i = 0; i < n_queries; i++) if (q_cnt[i]) P.n_tab[flavour_of(i)] += q_cnt[i];
+        for (int k = 0; k < 5; k++) { at[k] = acc; acc += P.n_tab[k]; }
+        P.work.resize(acc);
+        for (uint32_t i : by_cost) {
             if (q_cnt[i] == 0) continue;
-            auto& dst = *tabs[flavour_of(i)];
-            P.q[i].first_work = (uint32_t)(base[flavour_of(i)] + dst.size());
+            size_t& dst = at[flavour_of(i)];
+            P.q[i].first_work = (uint32_t)dst;
             P.q[i].n_work = q_cnt[i];
-            dst.insert(dst.end(), flat_work.begin() + q_begin[i], flat_work.begin() + q_begin[i] + q_cnt[i]);
+            std::copy(flat_work.begin() + q_begin[i], flat_work.begin() + q_begin[i] + q_cnt[i], P.work.begin() + dst);
+            dst += q_cnt[i];
         }
-        // merge sources: the work items' lists, or — more than 2 x 8 of them — group lists of 8 folded in parallel first (slots behind
-        // the work items' own)
-        const uint32_t G = 8;
-        uint32_t slot = (uint32_t)acc;
+    }
+
+    // merge sources: the work items' lists, or group lists of 8 folded in parallel first (slots behind the work items' own; kw_plan_policy.h)
+    void merge_sources() {
+        uint32_t slot = (uint32_t)P.work.size();
         for (uint32_t i = 0; i < n_queries; i++) {
             KwQueryDev& q = P.q[i];
             q.m_first = q.first_work; q.m_n = q.n_work;
-            if (q.n_work <= 2 * G) continue;
-            // many work items: kw_merge_kernel SELECTS the top k from their lists (kw_select_partials; cost independent of their number) —
-            // no groups; beyond its capacity the lists are folded in two levels as before
-            if (ctx->kw_merge_select_min && q.n_work >= ctx->kw_merge_select_min && q.n_work <= (uint32_t)KW_SEL_PMAX) continue;
+            if (!kw_policy_needs_merge_groups(q.n_work, ctx->kw_merge_select_min)) continue;
             q.m_first = slot;
-            q.m_n = (q.n_work + G - 1) / G;
-            for (uint32_t a = 0; a < q.n_work; a += G) P.groups.push_back({i, q.first_work + a, std::min(G, q.n_work - a), slot++});
+            q.m_n = (q.n_work + KW_MERGE_GROUP - 1) / KW_MERGE_GROUP;
+            for (uint32_t a = 0; a < q.n_work; a += KW_MERGE_GROUP) P.groups.push_back({i, q.first_work + a, std::min(KW_MERGE_GROUP, q.n_work - a), slot++});
         }
     }
+};
+}  // namespace
+
+static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query* queries, uint32_t n_queries, Plan& P, bool keep_ids, bool wildcard, const KwVFlat* vflat = nullptr,
+                      const uint16_t* present_elsewhere = nullptr) {
+    static const bool plan_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
+    const uint64_t tp0 = now_us();
+    P.q.resize(n_queries);
+    P.status.assign(n_queries, TSGPU_OK);
+    P.cutoff.assign(n_queries, 0);
+    BatchPlanner B{ctx, snap, queries, n_queries, P, keep_ids, wildcard, vflat, present_elsewhere, tp0,
+                   std::vector<QueryCut>(n_queries), std::vector<uint32_t>(n_queries, 0), std::vector<uint32_t>(n_queries, 0), std::vector<double>(n_queries, 0.0), {}};
+    const uint32_t min_par = ctx->plan_parallel_min_queries;
+    const uint32_t min_slice = std::max<uint32_t>(8, min_par / 8);                      // (256 queries per slice at the default threshold)
+    QuerySlices sl{n_queries, 1, 1};
+    if (min_par && n_queries >= min_par) sl.n_thr = std::min<uint32_t>((uint32_t)std::max(1, ctx->plan_threads), std::max<uint32_t>(1, n_queries / min_slice));
+    if (sl.n_thr > 1) sl.n_parts = std::min<uint32_t>(4 * sl.n_thr, std::max<uint32_t>(1, n_queries / std::max<uint32_t>(8, min_slice / 4)));
+    std::vector<PlanAcc> parts(sl.n_parts);
+    // per-query planning
+    for_query_slices(ctx, sl, [&](uint32_t k, uint32_t lo, uint32_t hi) { for (uint32_t i = lo; i < hi; i++) B.translate(i, lo, parts[k]); });
+    // driver blocks per work item: fixed by the option, or sized from the batch's driver blocks
+    uint32_t chunk = ctx->kw_chunk_blocks;
+    if (chunk == 0) {
+        uint64_t total_blocks = 0;
+        for (uint32_t i = 0; i < n_queries; i++) total_blocks += B.cut[i].chunk_blocks;
+        chunk = kw_policy_batch_chunk(total_blocks, (uint32_t)KW_MAX_CHUNK, n_queries, ctx->kw_merge_select_min);
+    }
+    for_query_slices(ctx, sl, [&](uint32_t k, uint32_t lo, uint32_t hi) { parts[k].flat_work.reserve((size_t)(hi - lo) * 4); for (uint32_t i = lo; i < hi; i++) B.cut_items(i, chunk, parts[k]); });
+    B.concatenate(parts, sl);
+    const uint64_t tp1 = now_us();
+    const std::vector<uint32_t> by_cost = B.cost_order();
+    const uint64_t tp2 = now_us();
+    B.layout_tables(by_cost);
+    B.merge_sources();
     if (plan_timing) fprintf(stderr, "[tsgpu] plan: per-query loop %llu us, cost sort %llu us, table layout %llu us\n", (unsigned long long)(tp1 - tp0),
                              (unsigned long long)(tp2 - tp1), (unsigned long long)(now_us() - tp2));
     return TSGPU_OK;
@@ -980,7 +950,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     auto scan = [&](uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; i++) {
             const tsgpu_kw_query& in = queries[i];
-            bool ok = in.n_fields == 1 && in.n_tokens >= 1 && in.n_tokens <= TSGPU_MAX_QUERY_TOKENS && in.n_dropped == 0 && in.n_filter == 0 && in.n_excluded == 0 &&
+            bool ok = in.n_fields == 1 && kw_token_count_ok(in) && in.n_dropped == 0 && in.n_filter == 0 && in.n_excluded == 0 &&
                       in.deadline_us == 0 && in.n_sort <= TSGPU_MAX_SORT_KEYS && in.match_type <= TSGPU_SUM_SCORE && in.field_ids[0] < 64;
             if (ok) { auto it = snap.field_is_array.find(in.field_ids[0]); ok = it != snap.field_is_array.end() && !it->second; }
             for (uint32_t k = 0; ok && k < in.n_sort; k++)
@@ -1003,13 +973,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     {
         const uint32_t min_par = ctx->plan_parallel_min_queries;
         const uint32_t n_thr = (min_par && n_queries >= min_par) ? std::min<uint32_t>((uint32_t)std::max(1, ctx->plan_threads), std::max<uint32_t>(1, n_queries / 512)) : 1;
-        if (n_thr <= 1) scan(0, n_queries);
-        else {
-            const uint32_t n_parts = 4 * n_thr;
-            std::atomic<uint32_t> next{0};
-            const std::function<void()> job = [&]() { for (;;) { const uint32_t k = next.fetch_add(1); if (k >= n_parts || bad.load()) break; scan((uint32_t)((uint64_t)n_queries * k / n_parts), (uint32_t)((uint64_t)n_queries * (k + 1) / n_parts)); } };
-            ctx->host_pool.run(job, (int)n_thr - 1);
-        }
+        for_query_slices(ctx, QuerySlices{n_queries, n_thr, n_thr <= 1 ? 1 : 4 * n_thr}, [&](uint32_t, uint32_t lo, uint32_t hi) { if (!bad.load()) scan(lo, hi); });
     }
     if (bad.load()) return TSGPU_OK;
     // device buffers: [KwQueryDev x n | one aux word | totals | six scratch arrays] in d_plan, the input records in d_plan_in
@@ -1371,11 +1335,10 @@ bool device_plan_applies(const tsgpu_ctx* ctx, const BatchOpts& bo, bool keep_id
 // fused kernel. A work item can yield at most one hit per driver id, so its segment of the hit buffer holds (blk_end - blk_begin) * 256
 // records of 1 + TMAX words; the items run in groups whose segments fit the budget.
 struct TablePlan { bool two = false; std::vector<uint64_t> hoff; std::vector<size_t> group_start{0}; uint64_t need = 0, records = 0; size_t rec_bytes = 0; };
-TablePlan group_hit_segments(const std::vector<KwWorkItem>& tab, size_t rec_bytes, uint64_t budget) {
+TablePlan group_hit_segments(const KwWorkItem* tab, size_t nws, size_t rec_bytes, uint64_t budget) {
     TablePlan tp;
     tp.rec_bytes = rec_bytes;
     auto records_of = [&](size_t i) { return (uint64_t)(tab[i].blk_end - tab[i].blk_begin) * BLOCK_IDS; };
-    const size_t nws = tab.size();
     for (size_t i = 0; i < nws; i++) { budget = std::max(budget, records_of(i)); tp.records += records_of(i); }
     tp.hoff.resize(nws);
     uint64_t used = 0;
@@ -1394,8 +1357,7 @@ struct HitTables {
     std::vector<uint32_t> oc_jobs[2];                                        // queries of the two multi-field tables that kw_mf_ordered_count_kernel counts
 };
 int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP, HitTables& H) {
-    const std::vector<KwWorkItem>* tabs[5] = {&P.work_small, &P.work_big, &P.work_mf_small, &P.work_mf_big, &P.work_wild};
-    for (int tb = 0; tb < 5; tb++) { H.n[tb] = DP.on && tb < 2 ? DP.n_work[tb] : tabs[tb]->size(); H.first[tb + 1] = H.first[tb] + H.n[tb]; }
+    for (int tb = 0; tb < 5; tb++) { H.n[tb] = DP.on && tb < 2 ? DP.n_work[tb] : P.n_tab[tb]; H.first[tb + 1] = H.first[tb] + H.n[tb]; }
     for (int tb = 0; tb < 4; tb++) {
         if (!H.n[tb] || !ctx->kw_two_kernels) continue;
         TablePlan& tp = H.tp[tb];
@@ -1405,7 +1367,7 @@ int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP,
             tp.need = tp.records = DP.hit_blocks[tb] * (uint64_t)BLOCK_IDS;
             if (int rc = L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) return rc;
         } else {
-            tp = group_hit_segments(*tabs[tb], rec_bytes, hit_budget_records(ctx, rec_bytes));
+            tp = group_hit_segments(P.work.data() + H.first[tb], H.n[tb], rec_bytes, hit_budget_records(ctx, rec_bytes));
             if (tp.two && L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) { (void)hipGetLastError(); tp.two = false; }      // no room for the hit buffer: the fused kernel needs none
             if (!tp.two) tp.hoff.clear();
         }
@@ -1422,6 +1384,32 @@ int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP,
     return TSGPU_OK;
 }
 
+// TESTS ONLY, option kw_plan_digest: the digests of this batch's plan (kw_plan_digest.h); the device planner's tables are read back for it
+int record_plan_digest(tsgpu_ctx* ctx, hipStream_t s, const Plan& P, const DevPlan& DP, const std::vector<KwWorkItem>& work, const HitTables& H, uint32_t n_queries) {
+    KwPlanTables t;
+    std::vector<KwQueryDev> q_dev; std::vector<KwWorkItem> w_dev; std::vector<uint64_t> hoff_dev;
+    if (DP.on) {
+        q_dev.resize(n_queries); w_dev.resize(H.first[5]); hoff_dev.resize(H.first[5]);
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        TSGPU_HIP_TRY(hipMemcpy(q_dev.data(), DP.dq, (size_t)n_queries * sizeof(KwQueryDev), hipMemcpyDeviceToHost));
+        if (H.first[5]) TSGPU_HIP_TRY(hipMemcpy(w_dev.data(), DP.dw, H.first[5] * sizeof(KwWorkItem), hipMemcpyDeviceToHost));
+        if (H.first[5]) TSGPU_HIP_TRY(hipMemcpy(hoff_dev.data(), DP.hoff, H.first[5] * 8, hipMemcpyDeviceToHost));
+    }
+    t.q = DP.on ? q_dev.data() : P.q.data(); t.status = P.status.data(); t.n_queries = n_queries;
+    t.mf = P.mf.data(); t.work = DP.on ? w_dev.data() : work.data();
+    t.groups = P.groups.data(); t.n_groups = P.groups.size();
+    for (int tb = 0; tb < 5; tb++) t.n_tab[tb] = H.n[tb];
+    for (int tb = 0; tb < 4; tb++) {
+        t.hoff[tb] = DP.on ? hoff_dev.data() + H.first[tb] : H.tp[tb].hoff.data();
+        t.n_hoff[tb] = DP.on ? (H.tp[tb].two ? H.n[tb] : 0) : H.tp[tb].hoff.size();
+    }
+    uint64_t cut, layout;
+    kw_plan_digests(t, cut, layout);
+    std::lock_guard<std::mutex> tl(ctx->tm_mu);
+    ctx->kw_last_plan_cut_digest = cut; ctx->kw_last_plan_layout_digest = layout;
+    return TSGPU_OK;
+}
+
 // the device-side tables of one batch: staging produces them, the launch, delivery and id-list phases consume them
 struct KwStaged {
     const KwQueryDev* dq = nullptr; const KwWorkItem* dw = nullptr; const uint32_t* daux = nullptr; const KwQueryMF* mf = nullptr;
@@ -1432,7 +1420,8 @@ struct KwStaged {
 
 // ---- the plan travels in ONE pinned staging buffer and ONE host-to-device copy (queries, work items, aux ids, multi-field
 //      descriptors, hit-record offsets): a pageable source costs a staged synchronous copy per call, five calls per batch ----
-int upload_plan_image(KwLane& L, hipStream_t s, const Plan& P, const DevPlan& DP, const std::vector<KwWorkItem>& work, const HitTables& H, KwStaged& T) {
+int upload_plan_image(KwLane& L, hipStream_t s, const Plan& P, const DevPlan& DP, const HitTables& H, KwStaged& T) {
+    const std::vector<KwWorkItem>& work = P.work;
     Placer place;
     const size_t at_q = place(P.q.size() * sizeof(KwQueryDev)), at_w = place(work.size() * sizeof(KwWorkItem)), at_aux = place(P.aux.size() * 4),
                  at_mf = place(P.mf.size() * sizeof(KwQueryMF));
@@ -1759,17 +1748,13 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
         const int cap = P.max_k + KW_THREADS <= 512 ? 512 : (P.max_k + KW_THREADS <= 1024 ? 1024 : 2048);
 
         // ---- staging: hit-buffer groups, the plan image, scratch, the outputs ----
-        std::vector<KwWorkItem> work(P.work_small);
-        work.insert(work.end(), P.work_big.begin(), P.work_big.end());
-        work.insert(work.end(), P.work_mf_small.begin(), P.work_mf_small.end());
-        work.insert(work.end(), P.work_mf_big.begin(), P.work_mf_big.end());
-        work.insert(work.end(), P.work_wild.begin(), P.work_wild.end());
         P.aux.push_back(0);
         HitTables H;
         if ((rc = plan_hit_tables(ctx, L, P, DP, H))) return rc;
+        if (ctx->kw_plan_digest && (rc = record_plan_digest(ctx, s, P, DP, P.work, H, n_queries))) return rc;
         const uint32_t n_work = (uint32_t)H.first[5];
         KwStaged T;
-        if ((rc = upload_plan_image(L, s, P, DP, work, H, T))) return rc;
+        if ((rc = upload_plan_image(L, s, P, DP, H, T))) return rc;
         L.last_tab_q = T.dq; L.last_tab_w = T.dw; L.last_tab_n_work = n_work;
         if ((rc = reserve_partials(L, (size_t)std::max<uint32_t>(n_work, 1) + P.groups.size(), KS, T.part))) return rc;
         if (keep_ids) {
@@ -1823,8 +1808,8 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
             ne.resize(n_work);
             TSGPU_HIP_TRY(hipMemcpy(ne.data(), T.part.n_emit, (size_t)n_work * 4, hipMemcpyDeviceToHost));
         }
-        if (bo.record_last) record_last_ids(L, P, work, ne, n_queries);
-        if (bo.id_lists && (rc = build_id_lists(L, s, P, work, ne, T.ids_out, n_queries, *bo.id_lists, bo.ids_dev, bo.ids_dev_done))) return rc;
+        if (bo.record_last) record_last_ids(L, P, P.work, ne, n_queries);
+        if (bo.id_lists && (rc = build_id_lists(L, s, P, P.work, ne, T.ids_out, n_queries, *bo.id_lists, bo.ids_dev, bo.ids_dev_done))) return rc;
         {
             const uint64_t t_end = now_us();
             ctx->kw_batches.fetch_add(1); ctx->kw_plan_us.fetch_add(t_planned - t_enter); ctx->kw_upload_us.fetch_add(t_uploaded - t_planned);
@@ -1861,35 +1846,14 @@ int tsgpu_keyword_aux_scores(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint
             KwQueryMF& m = mf[i];
             memset(&q, 0, sizeof q);
             memset(&m, 0xFF, sizeof m);
-            if (in.n_tokens == 0 || in.n_tokens > TSGPU_MAX_QUERY_TOKENS || in.n_fields == 0 || in.n_fields > (uint32_t)KW_MAX_FIELDS || in.match_type > TSGPU_SUM_SCORE)
+            if (!kw_token_count_ok(in) || !kw_field_count_ok(in) || in.match_type > TSGPU_SUM_SCORE)
                 return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_keyword_aux_scores: 1..10 tokens, 1..4 query_by fields");
-            m.n_fields = in.n_fields;
             m.driver_token = 0;
-            for (uint32_t f = 0; f < in.n_fields; f++) {
-                const auto fa = snap.field_is_array.find(in.field_ids[f]);
-                if (fa == snap.field_is_array.end()) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_keyword_aux_scores: unknown field");
-                m.is_array[f] = fa->second ? 1 : 0;
-                m.weight[f] = in.field_weights[f];
-            }
-            // one or_iterator per token that exists in some field (get_field_token_its, src/index.cpp:5598-5660), query order
-            uint32_t nl = 0;
-            for (uint32_t t = 0; t < in.n_tokens; t++) {
-                bool found = false;
-                for (uint32_t f = 0; f < in.n_fields; f++) {
-                    const uint32_t h = snap.find_handle(in.field_ids[f], in.term_ids[t]);
-                    if (h == 0xFFFFFFFFu) continue;
-                    m.list[nl][f] = h;
-                    found = true;
-                }
-                if (found) nl++;
-            }
-            q.n_lists = nl;
-            q.n_query_tokens = in.n_tokens;
-            q.match_type = in.match_type;
-            q.prio_exact = in.prioritize_exact_match; q.prio_pos = in.prioritize_token_position; q.prio_nfields = in.prioritize_num_matching_fields;
+            if (kw_fill_fields(snap, in, m)) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_keyword_aux_scores: unknown field");
+            kw_fill_token_lists(snap, in, false, q, m);
+            kw_fill_scoring(in, q);
             q.total_cost = 0;                                    // compute_aux_scores passes total_cost = 0, syn_orig_num_tokens = -1, no synonym flags (src/index.cpp:8826-8835)
-            q.syn_orig_num_tokens = -1;
-            q.weight = in.field_weights[0];
+            q.syn_orig_num_tokens = -1; q.orig_num_tokens = 0; q.is_synonym = 0; q.demote_synonym = 0;
             q.mf_index = i;
         }
         for (uint32_t i = 0; i < n_items; i++) if (item_query[i] >= n_queries) return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_aux_scores: item_query out of range");
@@ -2127,9 +2091,8 @@ int kw_terms_present(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n_q
     for (uint32_t i = 0; i < n_queries; i++) {
         const tsgpu_kw_query& in = queries[i];
         uint16_t m = 0;
-        for (uint32_t t = 0; t < in.n_tokens && t < TSGPU_MAX_QUERY_TOKENS; t++)
-            for (uint32_t f = 0; f < in.n_fields; f++)
-                if (sn && sn->find_handle(in.field_ids[f], in.term_ids[t]) != 0xFFFFFFFFu) { m |= (uint16_t)(1u << t); break; }
+        for (uint32_t t = 0; sn && t < in.n_tokens && t < TSGPU_MAX_QUERY_TOKENS; t++)
+            if (kw_resolve_token(*sn, in, in.term_ids[t]).found) m |= (uint16_t)(1u << t);
         masks[i] = m;
     }
     return TSGPU_OK;

@@ -72,7 +72,7 @@ static bool gb_loglog_cardinality_hist(const uint32_t* hist, uint64_t* out) {   
 }
 
 // tsgpu_kw_query -> the device description the scoring functions read, in the multi-field form (a single query_by field is the one-field case of
-// compute_aggregated_score); the checks are plan_batch's
+// compute_aggregated_score); the predicates and fills are kw_translate.h's, the order of the checks is this entry point's (sort slots first)
 static int gb_translate(const tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query& in, bool wildcard, KwQueryDev& q, KwQueryMF& m) {
     memset(&q, 0, sizeof q);
     memset(&m, 0xFF, sizeof m);
@@ -80,44 +80,14 @@ static int gb_translate(const tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_
     q.syn_orig_num_tokens = -1;
     if (in.n_sort > TSGPU_MAX_SORT_KEYS) return TSGPU_ERR_INVALID;
     if (const int sort_rc = check_sort_slots(const_cast<tsgpu_ctx*>(ctx), in.sort, in.n_sort, false, false, nullptr)) return sort_rc;
-    for (uint32_t s = 0; s < in.n_sort; s++) {
-        q.sort_kind[s] = in.sort[s].kind; q.sort_order[s] = in.sort[s].order; q.sort_col[s] = in.sort[s].column;
-    }
-    q.n_sort = (uint8_t)in.n_sort;
+    kw_fill_sort_slots(in, q);
     if (wildcard) { m.n_fields = 0; return TSGPU_OK; }
-    if (in.n_tokens == 0 || in.n_tokens > TSGPU_MAX_QUERY_TOKENS || in.n_fields == 0 || in.n_fields > (uint32_t)KW_MAX_FIELDS) return TSGPU_ERR_UNSUPPORTED;
-    if (in.n_dropped > TSGPU_MAX_DROPPED_TOKENS || in.n_tokens + in.n_dropped > TSGPU_MAX_QUERY_TOKENS) return TSGPU_ERR_UNSUPPORTED;
+    if (!kw_token_count_ok(in) || !kw_field_count_ok(in) || !kw_dropped_count_ok(in)) return TSGPU_ERR_UNSUPPORTED;
     if (in.match_type > TSGPU_SUM_SCORE) return TSGPU_ERR_INVALID;
-    m.n_fields = in.n_fields;
     m.driver_token = 0;
-    for (uint32_t f = 0; f < in.n_fields; f++) {
-        const auto fa = snap.field_is_array.find(in.field_ids[f]);
-        if (fa == snap.field_is_array.end()) return TSGPU_ERR_NOT_FOUND;
-        m.is_array[f] = fa->second ? 1 : 0;
-        m.weight[f] = in.field_weights[f];
-    }
-    uint32_t nl = 0;
-    auto add_token = [&](uint32_t term) {                // one or_iterator per token that exists in some field, query order (get_field_token_its, src/index.cpp:5598-5660)
-        bool found = false;
-        for (uint32_t f = 0; f < in.n_fields; f++) {
-            const uint32_t h = snap.find_handle(in.field_ids[f], term);
-            if (h == 0xFFFFFFFFu) continue;
-            m.list[nl][f] = h;
-            found = true;
-        }
-        if (found) nl++;
-    };
-    for (uint32_t t = 0; t < in.n_tokens; t++) add_token(in.term_ids[t]);
-    q.n_required = nl;
-    for (uint32_t t = 0; t < in.n_dropped; t++) add_token(in.dropped_term_ids[t]);        // after the query's own tokens (:5271-5290)
-    q.n_lists = nl;
-    q.n_query_tokens = in.n_tokens;
-    q.match_type = in.match_type;
-    q.prio_exact = in.prioritize_exact_match ? 1 : 0; q.prio_pos = in.prioritize_token_position ? 1 : 0; q.prio_nfields = in.prioritize_num_matching_fields ? 1 : 0;
-    q.total_cost = in.total_cost;
-    q.weight = in.field_weights[0];
-    q.syn_orig_num_tokens = (int8_t)((int)in.syn_orig_num_tokens_p1 - 1);
-    q.orig_num_tokens = in.orig_num_tokens; q.is_synonym = in.is_synonym_query ? 1 : 0; q.demote_synonym = in.demote_synonym_match ? 1 : 0;
+    if (const int rc = kw_fill_fields(snap, in, m)) return rc;
+    kw_fill_token_lists(snap, in, true, q, m);
+    kw_fill_scoring(in, q);
     return TSGPU_OK;
 }
 }  // namespace tsgpu

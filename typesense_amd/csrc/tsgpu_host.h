@@ -550,6 +550,8 @@ struct tsgpu_ctx {
     uint32_t kw_timing_min_queries = 64;             // keyword batches below this many queries skip the phase events (tsgpu_timings reports 0 ms for them)
     uint32_t kw_merge_select_min = 2;                // queries with at least this many partial lists are merged by selection (kw_select_partials: tree merge); 0 = always fold
     bool kw_count_touched = false;                   // measurement option: keyword batches launch the byte-counting instantiation of the find kernel
+    bool kw_plan_digest = false;                     // TESTS ONLY (option "kw_plan_digest"): keyword batches leave two digests of their plan (kw_plan_digest.h; under tm_mu)
+    uint64_t kw_last_plan_cut_digest = 0, kw_last_plan_layout_digest = 0;
     tsgpu_kw_touched kw_touched{};                   // ... and leave its counters here (tsgpu_kw_last_touched; under tm_mu)
     uint64_t kw_find_dir_items = 0, kw_find_pairs = 0, kw_find_dir_pairs = 0, kw_find_dir_wide_pairs = 0;     // ... and the directory-mode counts (tsgpu_get_counter; under tm_mu)
     std::atomic<uint64_t> kw_mf_pipelined_launches{0}, kw_candidates_rank_launches{0};
