@@ -149,6 +149,8 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * element i in lane i % lanes and adds the lanes left to right, so the bits of a distance depend on it;
  * "vec_prefilter" = 1 (default): bf16 bracket scan + exact fp32 re-score of the survivors, 0: fp32 MFMA scan of every row
  * (identical result sets either way), "vec_count_rescored" = 1: keep the vec_rescored_rows and vec_candidate_rows counters (costs two syncs);
+ * "vec_filter_direct_max" = 0 .. 65536 (default 65536): tsgpu_vec_knn_batch_filtered re-scores the rows of an allow list of at most this many ids
+ * directly instead of scanning (0 = every filtered query goes through the masked scan; identical results either way);
  * micro-batcher: "batch_max_queries" = calls with at most this many queries are coalesced with concurrent callers (default 64,
  * 0 = never), "batch_window_us" = how long a round's leader waits for the other threads that are inside the entry point to
  * park (default 10: a lane that is free should not idle; while every lane is busy callers keep parking and the rounds size
@@ -184,6 +186,9 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * it. Any valid plan gives the same hits; the digests let the tests see the plan itself (csrc/kw_plan_digest.h). Off: one branch per batch. */
 int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
 /* introspection counters (tests / bench): "vec_overflow_rounds", "vec_prefilter_groups", "vec_prefilter_fallbacks",
+ * "vec_filter_direct_queries" / "vec_filter_scan_queries" (filtered queries of tsgpu_vec_knn_batch_filtered answered by either route),
+ * "vec_filter_h2d_bytes" (bytes of id lists uploaded for them), "vec_filter_stage_us" / "vec_filter_build_us" (host time staging and uploading the lists / time of the
+ * bitmap and survivor-list build kernels; both kept under "vec_count_rescored"),
  * "vec_rescored_rows", "vec_candidate_rows" (rows of the last bracket group that reached the exact re-score / that passed the scan's tile-level bound),
  * "kw_last_hit_groups" (find+score groups of the last keyword batch, 0 = fused), "kw_last_hit_records",
  * "batch_rounds" / "batch_coalesced_calls" (micro-batcher: rounds executed / calls they served; "gb_batch_rounds" / "gb_batch_coalesced_calls": of grouped calls), host phase totals in us over all
@@ -521,6 +526,22 @@ uint64_t tsgpu_vec_count(tsgpu_ctx* ctx, uint32_t vec_field_id);
 int tsgpu_vec_knn_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k,
                         const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids, uint32_t n_excluded,
                         float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out);
+
+/* The same exact k-NN with ONE FILTER PER QUERY: filters[i] restricts query i only (NULL = no query is filtered), one pass over the rows
+ * serves the whole batch. Query i answers exactly as tsgpu_vec_knn_batch does for Q[i] alone with filters[i] (order, tie rule, distance bits,
+ * n_out); deleted rows are never returned, unknown labels in a list are ignored. Allow lists of at most "vec_filter_direct_max" ids are
+ * re-scored directly, the other queries share one masked scan. Small host-to-host calls from concurrent threads are coalesced exactly like
+ * tsgpu_vec_knn_batch's, and with them ("batch_max_queries"); tsgpu_hybrid_search_batch's vector pass is such a call. Not covered (they keep one pass per filtered query): the HNSW search, tsgpu_vector_search_batch's single parameter block, the
+ * tsgpu_group_* shard forms; filters must be host lists. */
+typedef struct tsgpu_vec_filter {
+    uint32_t filtered;              /* 0 = no allow list (all live rows); 1 = only allow_ids (n_allow == 0: nothing) */
+    uint32_t n_allow;
+    const uint32_t* allow_ids;      /* sorted seq_ids, host */
+    uint32_t n_excluded;
+    const uint32_t* excluded_ids;   /* sorted, host */
+} tsgpu_vec_filter;
+int tsgpu_vec_knn_batch_filtered(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k,
+                                 const tsgpu_vec_filter* filters, float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out);
 
 /* HNSW graph search (hnswlib::HierarchicalNSW<float>::searchKnnCloserFirst(q, k, ef, filter) of the Typesense fork, call site
  * src/index.cpp:3376-3445). The graph is a MIRROR of the server's hnswlib index (its construction stays in the reference's

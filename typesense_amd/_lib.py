@@ -63,6 +63,10 @@ class VecQueryC(C.Structure):
                 ("excluded_ids", C.c_void_p), ("flat_search_cutoff", C.c_uint64), ("query_doc_given", C.c_uint32), ("query_seq_id", C.c_uint32)]
 
 
+class VecFilterC(C.Structure):
+    _fields_ = [("filtered", C.c_uint32), ("n_allow", C.c_uint32), ("allow_ids", C.c_void_p), ("n_excluded", C.c_uint32), ("excluded_ids", C.c_void_p)]
+
+
 class HybridParamsC(C.Structure):
     _fields_ = [("k", C.c_uint32), ("fetch_size", C.c_uint32), ("alpha", C.c_float), ("distance_threshold", C.c_float), ("rerank_hybrid_matches", C.c_uint32)]
 
@@ -130,7 +134,7 @@ EXPORTS = [
     "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_destroy", "tsgpu_commit",
     "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_term_blocks_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
     "tsgpu_keyword_search_batch_ids", "tsgpu_keyword_search_grouped_batch", "tsgpu_keyword_search_grouped_candidates_batch", "tsgpu_id_lists_count", "tsgpu_id_lists_ids", "tsgpu_id_lists_free", "tsgpu_facet_set", "tsgpu_facet_count_batch", "tsgpu_facet_count_grouped_batch", "tsgpu_facet_range_count_batch", "tsgpu_facet_stats_batch", "tsgpu_facet_value_set", "tsgpu_facet_value_count_batch",
-    "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch",
+    "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch", "tsgpu_vec_knn_batch_filtered",
     "tsgpu_vec_hnsw_load", "tsgpu_vec_hnsw_enable", "tsgpu_vec_hnsw_build", "tsgpu_vec_hnsw_export", "tsgpu_vec_hnsw_search_batch", "tsgpu_vec_distances", "tsgpu_ip_distance", "tsgpu_vector_search_batch", "tsgpu_vector_search_batch_ids", "tsgpu_hybrid_search_batch", "tsgpu_hybrid_fuse_batch", "tsgpu_keyword_aux_scores", "tsgpu_merge_shard_hits", "tsgpu_merge_shard_hits_device", "tsgpu_last_timings", "tsgpu_last_aux_timings", "tsgpu_kw_last_touched", "tsgpu_kw_lists_footprint",
     "tsgpu_group_create_local", "tsgpu_group_unique_id", "tsgpu_group_create_rank", "tsgpu_group_create_rank_host", "tsgpu_group_destroy", "tsgpu_group_size", "tsgpu_group_keyword_search_batch", "tsgpu_group_keyword_search_candidates_batch", "tsgpu_group_wildcard_search_batch", "tsgpu_group_keyword_search_grouped_batch", "tsgpu_group_keyword_search_grouped_candidates_batch", "tsgpu_group_facet_count_batch", "tsgpu_group_facet_range_count_batch", "tsgpu_group_facet_stats_batch",
     "tsgpu_group_vec_knn_batch", "tsgpu_group_hybrid_search_batch", "tsgpu_group_last_timings", "tsgpu_group_set_option",
@@ -211,6 +215,7 @@ def lib(path=None):
     L.tsgpu_vec_count.argtypes = [vp, u32]
     L.tsgpu_vec_count.restype = u64
     L.tsgpu_vec_knn_batch.argtypes = [vp, u32, vp, i32, u32, u32, vp, u32, vp, u32, vp, vp, vp, i32]
+    L.tsgpu_vec_knn_batch_filtered.argtypes = [vp, u32, vp, i32, u32, u32, C.POINTER(VecFilterC), vp, vp, vp, i32]
     L.tsgpu_vec_hnsw_load.argtypes = [vp, u32, u32, C.c_int32, u32, vp, vp, vp, u32]
     L.tsgpu_vec_hnsw_enable.argtypes = [vp, u32, u32, u32, u32, u32]
     L.tsgpu_vec_hnsw_build.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, C.POINTER(HnswBuildInfoC)]

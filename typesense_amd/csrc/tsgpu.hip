@@ -426,6 +426,11 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
         return ok();
     }
     if (!strcmp(name, "vec_count_rescored")) { ctx->vec_count_rescored = value != 0; return ok(); }
+    if (!strcmp(name, "vec_filter_direct_max")) {
+        if (value < 0 || value > 65536) return fail(TSGPU_ERR_INVALID, "vec_filter_direct_max out of range (0..65536)");
+        ctx->vec_filter_direct_max = (uint32_t)value;
+        return ok();
+    }
     // micro-batcher (tsgpu_batcher.h): concurrent small calls are coalesced into one launch
     if (!strcmp(name, "index_min_slack_words")) { ctx->index_min_slack_words = (uint64_t)std::max<int64_t>(value, 0); return ok(); }   // (tests: small arenas)
     if (!strcmp(name, "index_compact_min_words")) { ctx->index_compact_min_words = (uint64_t)std::max<int64_t>(value, 0); return ok(); }   // (tests: small arenas)
@@ -466,6 +471,11 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "vec_overflow_rounds")) { *out = ctx->vec_overflow_rounds; return ok(); }
     if (!strcmp(name, "vec_prefilter_fallbacks")) { *out = ctx->vec_prefilter_fallbacks; return ok(); }
     if (!strcmp(name, "vec_prefilter_groups")) { *out = ctx->vec_prefilter_groups; return ok(); }
+    if (!strcmp(name, "vec_filter_direct_queries")) { *out = ctx->vec_filter_direct_queries; return ok(); }
+    if (!strcmp(name, "vec_filter_scan_queries")) { *out = ctx->vec_filter_scan_queries; return ok(); }
+    if (!strcmp(name, "vec_filter_h2d_bytes")) { *out = ctx->vec_filter_h2d_bytes; return ok(); }
+    if (!strcmp(name, "vec_filter_stage_us")) { *out = ctx->vec_filter_stage_us; return ok(); }
+    if (!strcmp(name, "vec_filter_build_us")) { *out = ctx->vec_filter_build_us; return ok(); }
     if (!strcmp(name, "vec_rescored_rows")) { *out = ctx->vec_rescored_rows; return ok(); }
     if (!strcmp(name, "vec_candidate_rows")) { *out = ctx->vec_candidate_rows; return ok(); }
     if (!strcmp(name, "hnsw_last_expansions")) { *out = ctx->hnsw_last_expansions; return ok(); }

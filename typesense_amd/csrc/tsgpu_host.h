@@ -581,6 +581,10 @@ struct tsgpu_ctx {
     uint32_t vec_ip_lanes = 4;                       // order of the exact distances' sums: 4 = hnswlib built for SSE (the reference's stock flags), 8 = AVX, 16 = AVX-512
     uint32_t vec_prefilter = 1;                      // 1 = bf16 bracket scan + exact fp32 re-score (default); 0 = fp32 MFMA scan
     uint64_t vec_prefilter_groups = 0;               // query groups answered by the bf16 bracket path
+    uint32_t vec_filter_direct_max = 65536;          // tsgpu_vec_knn_batch_filtered: allow lists of at most this many ids skip the scan (re-scored directly); 0 = every filtered query is scanned
+    uint64_t vec_filter_direct_queries = 0, vec_filter_scan_queries = 0;   // counters: filtered queries answered by either route
+    uint64_t vec_filter_h2d_bytes = 0;               // counter: bytes of id lists (+ their offsets) uploaded for per-query filters
+    uint64_t vec_filter_stage_us = 0, vec_filter_build_us = 0;   // counters: host time staging + uploading the lists / time of the bitmap or survivor-list build kernels that follow (only under vec_count_rescored: it costs a sync per group)
     int hnsw_test_tiny_cand = 0;                      // TESTS ONLY (option "hnsw_test_tiny_cand"): searches with max(ef, k) <= 128 start on a 24-entry candidate heap, so that
                                                      // the re-run of the overflowed queries on the largest tier is exercised on small graphs
     uint32_t hnsw_test_slots = 0;                    // TESTS ONLY (option "hnsw_test_slots"): when non-zero, caps the concurrent query slots of an HNSW search (4 096

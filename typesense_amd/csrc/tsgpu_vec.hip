@@ -34,6 +34,7 @@ struct VecField {
     // scratch
     DevBuf d_dense, d_cand, d_cand_cnt, d_tau, dQ, d_dist, d_lab, d_cnt, d_mask, d_rows, d_q1, d_out1;
     DevBuf d_Qh, d_cq, d_L1, d_lbkey, d_surv, d_surv_cnt, d_gkeys;
+    DevBuf d_qbits, d_qoff, d_frows, d_fptr, d_perm, d_Qperm, d_pdist, d_plab, d_pcnt;   // per-query filters: bitmaps, their offsets, id lists (CSR), caller-order permutation + permuted I/O
     uint64_t seg_cap_hint = 0;                         // the largest (slab, query) candidate-segment capacity this field's data has needed so far
     // HNSW graph mirror (tsgpu_vec_hnsw_load): hnswlib's link lists; rows = hnswlib internal ids
     DevBuf g_link0, g_upper_ptr, g_upper_links, g_visited, g_vhash, g_stat, g_sel;
@@ -59,7 +60,7 @@ struct VecField {
     }
     void release() {
         DevBuf* b[] = {&X, &labels, &row_ok, &Xh, &xnorm, &tile_nmax, &d_dense, &d_cand, &d_cand_cnt, &d_tau, &dQ, &d_dist, &d_lab, &d_cnt, &d_mask, &d_rows,
-                       &d_q1, &d_out1, &d_Qh, &d_cq, &d_L1, &d_lbkey, &d_surv, &d_surv_cnt, &d_gkeys, &g_link0, &g_upper_ptr, &g_upper_links, &g_visited, &g_vhash, &g_stat, &g_sel};
+                       &d_q1, &d_out1, &d_Qh, &d_cq, &d_L1, &d_lbkey, &d_surv, &d_surv_cnt, &d_gkeys, &d_qbits, &d_qoff, &d_frows, &d_fptr, &d_perm, &d_Qperm, &d_pdist, &d_plab, &d_pcnt, &g_link0, &g_upper_ptr, &g_upper_links, &g_visited, &g_vhash, &g_stat, &g_sel};
         for (auto* x : b) x->release();
     }
 };
@@ -96,8 +97,9 @@ static VecField* get_field(tsgpu_ctx* ctx, uint32_t id) {
 
 // the exact k-NN launch sequence (vec_kernels.hip.h header); caller holds ctx->mu.
 // Q_dev: [n_q][dim] on the device (already normalised for cosine). Outputs [n_q][k] on the device.
+// qm: per-query row bitmaps of the group (tsgpu_vec_knn_batch_filtered), null = the one shared mask (the kernels an unfiltered batch always ran).
 static int knn_group(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n_q, uint32_t k, const uint8_t* mask_dev,
-                     float* dist_dev, uint64_t* label_dev, uint32_t* cnt_dev, bool record_events) {
+                     float* dist_dev, uint64_t* label_dev, uint32_t* cnt_dev, bool record_events, const VecQMasks* qm = nullptr) {
     hipStream_t s = ctx->stream;
     const uint32_t n_rows = (uint32_t)f->n_rows;
     const uint32_t n_tiles = (n_rows + VEC_ROWS - 1) / VEC_ROWS;
@@ -121,6 +123,11 @@ static int knn_group(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n
         n_slabs = std::max<uint32_t>(8, (n_slabs + 7) / 8 * 8);
         a.ord_per_slab = per; a.n_slabs = n_slabs; a.n_qtiles = n_qtiles;
         const dim3 grid(n_slabs * n_qtiles), block(VEC_THREADS);
+        if (qm) {
+            if (wide) { if (aligned) hipLaunchKernelGGL((vec_scan_kernel<2, true, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((vec_scan_kernel<2, false, true>), grid, block, 0, s, a); }
+            else { if (aligned) hipLaunchKernelGGL((vec_scan_kernel<1, true, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((vec_scan_kernel<1, false, true>), grid, block, 0, s, a); }
+            return;
+        }
         if (wide) { if (aligned) hipLaunchKernelGGL((vec_scan_kernel<2, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((vec_scan_kernel<2, false>), grid, block, 0, s, a); }
         else { if (aligned) hipLaunchKernelGGL((vec_scan_kernel<1, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((vec_scan_kernel<1, false>), grid, block, 0, s, a); }
     };
@@ -128,6 +135,7 @@ static int knn_group(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n
     memset(&base, 0, sizeof base);
     base.X = f->X.as<float>(); base.row_ok = mask_dev; base.Q = Q_dev;
     base.n_rows = n_rows; base.dim = f->dim; base.n_q = n_q;
+    if (qm) base.qm = *qm;
 
     if (record_events) TSGPU_HIP_TRY(hipEventRecord(ctx->ev[3], s));
     if (n_tiles <= sample_tiles) {
@@ -215,7 +223,7 @@ static int vec_refresh_mirror(VecField* f, uint32_t row0, uint32_t n, uint64_t n
 static const uint32_t VEC_SURV_CAP = 65536;
 static const uint32_t VEC_REFINE_GCAP = 4 * VEC_SURV_CAP - VEC_REFINE_LCAP;      // candidates per query beyond the refine kernel's LDS list
 static int knn_group_prefilter(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n_q, uint32_t k, const uint8_t* mask_dev,
-                               float* dist_dev, uint64_t* label_dev, uint32_t* cnt_dev, bool record_events) {
+                               float* dist_dev, uint64_t* label_dev, uint32_t* cnt_dev, bool record_events, const VecQMasks* qm = nullptr) {
     hipStream_t s = ctx->stream;
     const uint32_t n_rows = (uint32_t)f->n_rows;
     const uint32_t n_tiles = (n_rows + VEC_ROWS - 1) / VEC_ROWS;
@@ -248,6 +256,12 @@ static int knn_group_prefilter(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
         geometry(a.n_ord, target_wgs, a.ord_per_slab, a.n_slabs);
         a.n_qtiles = n_qtiles;
         const dim3 grid(a.n_slabs * n_qtiles), block(VEC_HTHREADS);
+        if (qm) {
+            if (QT == 256) hipLaunchKernelGGL((vec_hscan_kernel<4, true>), grid, block, 0, s, a);
+            else if (QT == 128) hipLaunchKernelGGL((vec_hscan_kernel<2, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((vec_hscan_kernel<1, true>), grid, block, 0, s, a);
+            return;
+        }
         if (QT == 256) hipLaunchKernelGGL((vec_hscan_kernel<4>), grid, block, 0, s, a);
         else if (QT == 128) hipLaunchKernelGGL((vec_hscan_kernel<2>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((vec_hscan_kernel<1>), grid, block, 0, s, a);
@@ -261,6 +275,7 @@ static int knn_group_prefilter(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
     base.Xh = f->Xh.as<uint16_t>(); base.row_ok = mask_dev; base.Qh = f->d_Qh.as<uint16_t>(); base.tile_nmax = f->tile_nmax.as<float>();
     base.n_q_pad = n_q_pad;
     base.cq = f->d_cq.as<float>(); base.n_rows = n_rows; base.dimp = f->dimp; base.n_q = n_q; base.L1 = f->d_L1.as<float>();
+    if (qm) base.qm = *qm;
 
     // pass 1: strided sample of the row tiles (all of them for a small index) -> L1[q] = k-th largest group maximum of the
     // sample's lower bounds
@@ -323,7 +338,7 @@ static int knn_group_prefilter(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
         // brackets cannot separate this data (mass ties / more near-duplicates than the survivor arena): the fp32 scan's
         // (distance, row) keys converge on any input — run the group there
         ctx->vec_prefilter_fallbacks++;
-        return knn_group(ctx, f, Q_dev, n_q, k, mask_dev, dist_dev, label_dev, cnt_dev, record_events);
+        return knn_group(ctx, f, Q_dev, n_q, k, mask_dev, dist_dev, label_dev, cnt_dev, record_events, qm);
     }
     // exact re-score of the survivors (hnswlib's summation order) and final selection
     hipLaunchKernelGGL(vec_rescore_kernel, dim3(n_q, 4), dim3(VEC_THREADS), 0, s, (const float*)f->X.as<float>(), Q_dev, f->dim,
@@ -380,6 +395,180 @@ static void knn_collect_timings(tsgpu_ctx* ctx) {
     ctx->timings.vec_merge_ms = b;
     ctx->timings.total_ms = a + b;
     ctx->timings.vec_scan_ms = c;
+}
+
+
+// ---------------------------------------------------------------- per-query filters (tsgpu_vec_knn_batch_filtered)
+// One query's lists as sorted ROWS appended to `rows`. While the field is in identity mode label == row: the ids go up as they are (the
+// kernels bounds-check them); otherwise they are translated with find_row, as build_mask does, and sorted. A list the caller did not sort is sorted here.
+static void filter_rows_of(const VecField* f, const uint32_t* ids, uint32_t n, std::vector<uint32_t>& rows) {
+    const size_t at = rows.size();
+    if (f->identity) {
+        rows.insert(rows.end(), ids, ids + n);
+        if (!std::is_sorted(rows.begin() + at, rows.end())) std::sort(rows.begin() + at, rows.end());
+        return;
+    }
+    uint32_t row;
+    for (uint32_t i = 0; i < n; i++) if (f->find_row(ids[i], row)) rows.push_back(row);
+    std::sort(rows.begin() + at, rows.end());
+}
+
+// CSR of the lists of the filtered queries idx[0..n) on the device (f->d_frows / f->d_fptr); caller holds ctx->mu
+static int upload_filter_lists(tsgpu_ctx* ctx, VecField* f, const tsgpu_vec_filter* filters, const uint32_t* idx, uint32_t n, VecFilterLists& L) {
+    std::vector<uint32_t> rows;
+    std::vector<uint64_t> ptr(2 * (size_t)n + 2);
+    std::vector<uint8_t> flt(n);
+    size_t total = 0;
+    for (uint32_t i = 0; i < n; i++) total += (size_t)(filters[idx[i]].filtered ? filters[idx[i]].n_allow : 0) + filters[idx[i]].n_excluded;
+    rows.reserve(total);
+    for (uint32_t i = 0; i < n; i++) {
+        const tsgpu_vec_filter& fl = filters[idx[i]];
+        flt[i] = fl.filtered ? 1 : 0;
+        ptr[i] = rows.size();
+        if (fl.filtered && fl.n_allow) filter_rows_of(f, fl.allow_ids, fl.n_allow, rows);
+    }
+    ptr[n] = rows.size();
+    for (uint32_t i = 0; i < n; i++) {
+        const tsgpu_vec_filter& fl = filters[idx[i]];
+        ptr[n + 1 + i] = rows.size();
+        if (fl.n_excluded) filter_rows_of(f, fl.excluded_ids, fl.n_excluded, rows);
+    }
+    ptr[2 * (size_t)n + 1] = rows.size();
+    int rc;
+    const size_t ptr_bytes = ptr.size() * 8;
+    if ((rc = f->d_frows.reserve(std::max<size_t>(rows.size() * 4, 16)))) return rc;
+    if ((rc = f->d_fptr.reserve(ptr_bytes + n + 16))) return rc;
+    hipStream_t s = ctx->stream;
+    if (!rows.empty()) TSGPU_HIP_TRY(hipMemcpyAsync(f->d_frows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
+    TSGPU_HIP_TRY(hipMemcpyAsync(f->d_fptr.p, ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
+    TSGPU_HIP_TRY(hipMemcpyAsync((uint8_t*)f->d_fptr.p + ptr_bytes, flt.data(), n, hipMemcpyHostToDevice, s));
+    TSGPU_HIP_TRY(hipStreamSynchronize(s));                 // the staging vectors die with this frame
+    ctx->vec_filter_h2d_bytes += rows.size() * 4 + ptr_bytes + n;
+    L.rows = f->d_frows.as<uint32_t>();
+    L.allow_ptr = f->d_fptr.as<uint64_t>();
+    L.excl_ptr = f->d_fptr.as<uint64_t>() + n + 1;
+    L.filtered = (const uint8_t*)f->d_fptr.p + ptr_bytes;
+    return TSGPU_OK;
+}
+
+static bool filter_restricts(const tsgpu_vec_filter& fl) { return fl.filtered || fl.n_excluded; }
+
+// Exact k-NN of n_q queries with one filter each; Q_dev as knn_device takes it, outputs [n_q][k] on the device in caller order. Caller holds ctx->mu.
+//   direct queries  allow list of <= vec_filter_direct_max ids (bracket path only: its exact re-score is what they run on): vec_direct_fill_kernel writes
+//                   their live, not excluded rows into the survivor arena, vec_rescore_kernel + vec_select_kernel finish — no scan;
+//   scan queries    everything else, unfiltered queries included: groups of <= 512 share one scan; a filtered query owns a row bitmap
+//                   (vec_qmask_build_kernel), the bitmap arena is bounded like the candidate arena (4 GiB), a group shrinks to fit.
+// The batch is permuted (scan queries first, then direct ones, caller order inside each) and the outputs are put back.
+static int knn_device_filtered(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n_q, uint32_t k, const tsgpu_vec_filter* filters,
+                               float* dist_dev, uint64_t* label_dev, uint32_t* cnt_dev) {
+    hipStream_t s = ctx->stream;
+    const uint32_t GROUP = 512;
+    const uint32_t n_rows = (uint32_t)f->n_rows;
+    const uint32_t n_tiles = (n_rows + VEC_ROWS - 1) / VEC_ROWS;
+    const uint32_t words = 4 * n_tiles;
+    const uint64_t arena_limit = 4ull << 30;
+    const uint8_t* shared_mask = f->any_deleted ? f->row_ok.as<uint8_t>() : nullptr;
+    const uint32_t direct_max = ctx->vec_prefilter ? ctx->vec_filter_direct_max : 0;
+    std::vector<uint32_t> perm, direct;
+    perm.reserve(n_q);
+    for (uint32_t q = 0; q < n_q; q++) {
+        if (filters[q].filtered && direct_max && filters[q].n_allow <= direct_max) direct.push_back(q);
+        else perm.push_back(q);
+    }
+    const uint32_t n_scan = (uint32_t)perm.size(), n_direct = (uint32_t)direct.size();
+    perm.insert(perm.end(), direct.begin(), direct.end());
+    bool permuted = false;
+    for (uint32_t i = 0; i < n_q && !permuted; i++) permuted = perm[i] != i;
+    int rc;
+    const float* Qp = Q_dev;
+    float* pd = dist_dev; uint64_t* pl = label_dev; uint32_t* pc = cnt_dev;
+    if (permuted) {
+        if ((rc = f->d_perm.reserve((size_t)n_q * 4)) || (rc = f->d_Qperm.reserve((size_t)n_q * f->dim * 4)) || (rc = f->d_pdist.reserve((size_t)n_q * k * 4)) ||
+            (rc = f->d_plab.reserve((size_t)n_q * k * 8)) || (rc = f->d_pcnt.reserve((size_t)n_q * 4))) return rc;
+        TSGPU_HIP_TRY(hipMemcpyAsync(f->d_perm.p, perm.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL((vec_permute_rows_kernel<float>), dim3((uint32_t)(((uint64_t)n_q * f->dim + 255) / 256)), dim3(256), 0, s, Q_dev, f->d_Qperm.as<float>(),
+                           (const uint32_t*)f->d_perm.as<uint32_t>(), n_q, f->dim, 0);
+        Qp = f->d_Qperm.as<float>(); pd = f->d_pdist.as<float>(); pl = f->d_plab.as<uint64_t>(); pc = f->d_pcnt.as<uint32_t>();
+    }
+    ctx->scan_events_valid = false;
+    const bool timed = ctx->vec_count_rescored != 0;
+    auto now_us = []() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    // ---- scan queries
+    const uint64_t map_bytes = (uint64_t)words * 4;
+    const uint32_t max_maps = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(GROUP, arena_limit / std::max<uint64_t>(map_bytes, 1)));
+    bool first = true;
+    for (uint32_t g0 = 0; g0 < n_scan;) {
+        // the group: up to GROUP queries, of which at most max_maps own a bitmap
+        uint32_t g1 = g0, n_maps = 0;
+        std::vector<uint32_t> owners, qoff;
+        while (g1 < n_scan && g1 - g0 < GROUP) {
+            const bool own = filter_restricts(filters[perm[g1]]);
+            if (own && n_maps == max_maps) break;
+            qoff.push_back(own ? n_maps : VEC_QMASK_NONE);
+            if (own) { owners.push_back(perm[g1]); n_maps++; }
+            g1++;
+        }
+        const uint32_t nq = g1 - g0;
+        VecQMasks qm{nullptr, nullptr, words};
+        if (n_maps) {
+            const uint64_t t0 = timed ? now_us() : 0;
+            VecFilterLists L;
+            if ((rc = upload_filter_lists(ctx, f, filters, owners.data(), n_maps, L))) return rc;
+            const uint64_t t1 = timed ? now_us() : 0;
+            if ((rc = f->d_qbits.reserve((size_t)n_maps * map_bytes)) || (rc = f->d_qoff.reserve((size_t)nq * 4))) return rc;
+            TSGPU_HIP_TRY(hipMemcpyAsync(f->d_qoff.p, qoff.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(vec_qmask_build_kernel, dim3((uint32_t)(((uint64_t)n_maps * words + 255) / 256)), dim3(256), 0, s, L, f->row_ok.as<uint8_t>(), n_rows, words, n_maps,
+                               f->d_qbits.as<uint32_t>());
+            TSGPU_HIP_TRY(hipGetLastError());
+            TSGPU_HIP_TRY(hipStreamSynchronize(s));         // qoff's staging vector dies with this iteration
+            if (timed) { ctx->vec_filter_stage_us += t1 - t0; ctx->vec_filter_build_us += now_us() - t1; }
+            qm.bits = f->d_qbits.as<uint32_t>(); qm.off = f->d_qoff.as<uint32_t>();
+            ctx->vec_filter_scan_queries += n_maps;
+        }
+        const VecQMasks* qmp = n_maps ? &qm : nullptr;
+        rc = ctx->vec_prefilter
+            ? knn_group_prefilter(ctx, f, Qp + (size_t)g0 * f->dim, nq, k, shared_mask, pd + (size_t)g0 * k, pl + (size_t)g0 * k, pc + g0, first, qmp)
+            : knn_group(ctx, f, Qp + (size_t)g0 * f->dim, nq, k, shared_mask, pd + (size_t)g0 * k, pl + (size_t)g0 * k, pc + g0, first, qmp);
+        if (rc) return rc;
+        first = false;
+        g0 = g1;
+    }
+    // ---- direct queries
+    for (uint32_t g0 = 0; g0 < n_direct; g0 += GROUP) {
+        const uint32_t nq = std::min<uint32_t>(GROUP, n_direct - g0), at = n_scan + g0;
+        const uint64_t t0 = timed ? now_us() : 0;
+        uint32_t stride = 1;
+        for (uint32_t i = 0; i < nq; i++) stride = std::max(stride, filters[direct[g0 + i]].n_allow);
+        VecFilterLists L;
+        if ((rc = upload_filter_lists(ctx, f, filters, direct.data() + g0, nq, L))) return rc;
+        const uint64_t t1 = timed ? now_us() : 0;
+        if ((rc = f->d_surv.reserve((size_t)nq * stride * 4)) || (rc = f->d_dense.reserve((size_t)nq * stride * 8)) || (rc = f->d_surv_cnt.reserve((size_t)nq * 4 + 16)) ||
+            (rc = f->d_tau.reserve((size_t)nq * 8))) return rc;
+        if (first && g0 == 0) TSGPU_HIP_TRY(hipEventRecord(ctx->ev[3], s));      // (a batch without a scan: the timing events bracket its first direct group)
+        TSGPU_HIP_TRY(hipMemsetAsync(f->d_surv_cnt.p, 0, (size_t)nq * 4 + 16, s));
+        hipLaunchKernelGGL(vec_direct_fill_kernel, dim3(nq), dim3(256), 0, s, L, shared_mask, n_rows, f->d_surv.as<uint32_t>(), (size_t)stride, f->d_surv_cnt.as<uint32_t>());
+        if (timed) { TSGPU_HIP_TRY(hipStreamSynchronize(s)); ctx->vec_filter_stage_us += t1 - t0; ctx->vec_filter_build_us += now_us() - t1; }
+        hipLaunchKernelGGL(vec_rescore_kernel, dim3(nq, 4), dim3(VEC_THREADS), 0, s, (const float*)f->X.as<float>(), Qp + (size_t)at * f->dim, f->dim,
+                           (const uint32_t*)f->d_surv.as<uint32_t>(), (const uint32_t*)f->d_surv_cnt.as<uint32_t>(), (size_t)stride, f->d_dense.as<uint64_t>(), ctx->vec_ip_lanes);
+        if (first && g0 == 0) TSGPU_HIP_TRY(hipEventRecord(ctx->ev[4], s));
+        hipLaunchKernelGGL(vec_select_kernel, dim3(nq), dim3(VEC_THREADS), 0, s, (const uint64_t*)f->d_dense.as<uint64_t>(), (size_t)stride,
+                           (const uint32_t*)f->d_surv_cnt.as<uint32_t>(), stride, k, 0, f->labels.as<uint64_t>(), pd + (size_t)at * k, pl + (size_t)at * k, pc + at,
+                           f->d_tau.as<uint64_t>(), f->d_surv_cnt.as<uint32_t>() + nq);
+        if (first && g0 == 0) TSGPU_HIP_TRY(hipEventRecord(ctx->ev[5], s));
+        TSGPU_HIP_TRY(hipGetLastError());
+        ctx->vec_filter_direct_queries += nq;
+    }
+    if (permuted) {
+        const uint32_t blocks = (uint32_t)(((uint64_t)n_q * k + 255) / 256);
+        hipLaunchKernelGGL((vec_permute_rows_kernel<float>), dim3(blocks), dim3(256), 0, s, (const float*)pd, dist_dev, (const uint32_t*)f->d_perm.as<uint32_t>(), n_q, k, 1);
+        hipLaunchKernelGGL((vec_permute_rows_kernel<uint64_t>), dim3(blocks), dim3(256), 0, s, (const uint64_t*)pl, label_dev, (const uint32_t*)f->d_perm.as<uint32_t>(), n_q, k, 1);
+        hipLaunchKernelGGL((vec_permute_rows_kernel<uint32_t>), dim3((n_q + 255) / 256), dim3(256), 0, s, (const uint32_t*)pc, cnt_dev, (const uint32_t*)f->d_perm.as<uint32_t>(), n_q, 1u, 1);
+        TSGPU_HIP_TRY(hipGetLastError());
+    }
+    ctx->timings.vec_flops = 2ull * f->n_rows * f->dim * std::min<uint32_t>(n_scan, GROUP);
+    ctx->timings.vec_scan_bytes = !n_scan ? 0 : ctx->vec_prefilter ? (uint64_t)f->n_rows * f->dimp * 2 + (uint64_t)std::min<uint32_t>(n_scan, GROUP) * f->dimp * 2
+                                                                   : (uint64_t)f->n_rows * f->dim * 4 + (uint64_t)std::min<uint32_t>(n_scan, GROUP) * f->dim * 4;
+    return TSGPU_OK;
 }
 
 // row mask for deleted rows / allow list / excluded ids; returns nullptr (all rows ok) when nothing restricts
@@ -647,18 +836,32 @@ struct VecRequest : ParkedRequest {
     uint32_t field = 0, k = 0;
     const float* Q = nullptr;                        // host, [units][dim]
     float* dist_out = nullptr; uint64_t* label_out = nullptr; uint32_t* n_out = nullptr;   // host
+    const tsgpu_vec_filter* filters = nullptr;       // [units] the caller's filters, null = none (they stay valid: the caller blocks until its round is done)
 };
+}
+static int vec_knn_filtered_locked(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, const tsgpu_vec_filter* filters,
+                                   float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out);
+// a filter that counts ids must have its list; any = some query of the batch is restricted
+static int check_filters(const tsgpu_vec_filter* filters, uint32_t n_q, bool& any) {
+    any = false;
+    if (filters) for (uint32_t q = 0; q < n_q; q++) {
+        if ((filters[q].filtered && filters[q].n_allow && !filters[q].allow_ids) || (filters[q].n_excluded && !filters[q].excluded_ids))
+            return fail(TSGPU_ERR_INVALID, "tsgpu_vec_knn_batch_filtered: a filter counts ids but its list is NULL");
+        any = any || filter_restricts(filters[q]);
+    }
+    return TSGPU_OK;
 }
 static int vec_knn_locked(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, const uint32_t* allow_ids,
                           uint32_t n_allow, const uint32_t* excluded_ids, uint32_t n_excluded, float* dist_out, uint64_t* label_out,
                           uint32_t* n_out, int mem_out);
 
-// A small unfiltered k-NN call from one of several concurrent request threads (the reference: vecdex->searchKnnCloserFirst per
+// A small k-NN call (with or without its own allow list / excluded ids) from one of several concurrent request threads (the reference: vecdex->searchKnnCloserFirst per
 // request thread, src/index.cpp:3384-3386): the parked calls of one (field, k) run as ONE batch — one pass over the row matrix
 // serves all of them, which is where the batched scan's throughput comes from.
-static int vec_knn_coalesced(tsgpu_ctx* ctx, uint32_t field, const float* Q, uint32_t n_q, uint32_t k, float* dist_out, uint64_t* label_out, uint32_t* n_out) {
+static int vec_knn_coalesced(tsgpu_ctx* ctx, uint32_t field, const float* Q, uint32_t n_q, uint32_t k, const tsgpu_vec_filter* filters, float* dist_out, uint64_t* label_out,
+                             uint32_t* n_out) {
     VecRequest me;
-    me.units = n_q; me.field = field; me.k = k; me.Q = Q; me.dist_out = dist_out; me.label_out = label_out; me.n_out = n_out;
+    me.units = n_q; me.field = field; me.k = k; me.Q = Q; me.dist_out = dist_out; me.label_out = label_out; me.n_out = n_out; me.filters = filters;
     typedef std::unique_lock<std::mutex> Lock;
     auto acquire = [&]() { return std::unique_ptr<Lock>(new Lock(ctx->mu)); };
     const uint32_t round_cap = std::max<uint32_t>(ctx->batch_round_queries, n_q);
@@ -687,7 +890,16 @@ static int vec_knn_coalesced(tsgpu_ctx* ctx, uint32_t field, const float* Q, uin
                 std::vector<uint32_t> c(total);
                 uint32_t at = 0;
                 for (VecRequest* r : round) { memcpy(Qall.data() + (size_t)at * f->dim, r->Q, (size_t)r->units * f->dim * 4); at += r->units; }
-                rc = vec_knn_locked(ctx, round[0]->field, Qall.data(), TSGPU_MEM_HOST, total, kk, nullptr, 0, nullptr, 0, d.data(), l.data(), c.data(), TSGPU_MEM_HOST);
+                // a round that holds a filtered call runs as ONE filtered batch: every query carries its own lists
+                bool any_filtered = false;
+                for (VecRequest* r : round) any_filtered = any_filtered || r->filters;
+                std::vector<tsgpu_vec_filter> fl;
+                if (any_filtered) for (VecRequest* r : round) {
+                    if (r->filters) fl.insert(fl.end(), r->filters, r->filters + r->units);
+                    else fl.insert(fl.end(), r->units, tsgpu_vec_filter{0, 0, nullptr, 0, nullptr});
+                }
+                rc = fl.empty() ? vec_knn_locked(ctx, round[0]->field, Qall.data(), TSGPU_MEM_HOST, total, kk, nullptr, 0, nullptr, 0, d.data(), l.data(), c.data(), TSGPU_MEM_HOST)
+                                : vec_knn_filtered_locked(ctx, round[0]->field, Qall.data(), TSGPU_MEM_HOST, total, kk, fl.data(), d.data(), l.data(), c.data(), TSGPU_MEM_HOST);
                 if (rc != TSGPU_OK) err = tls_error();
                 else {
                     at = 0;
@@ -717,10 +929,30 @@ int tsgpu_vec_knn_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, i
     if (k == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_knn_batch: k must be > 0");
     if (k > TSGPU_MAX_TOPK) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_knn_batch: k > TSGPU_MAX_TOPK is not accelerated");
     struct CallerCount { std::atomic<int>& c; explicit CallerCount(std::atomic<int>& x) : c(x) { c.fetch_add(1); } ~CallerCount() { c.fetch_sub(1); } } cc(ctx->vec_callers);
-    if (mem_q == TSGPU_MEM_HOST && mem_out == TSGPU_MEM_HOST && !allow_ids && n_excluded == 0 && n_q <= ctx->batch_max_queries && ctx->vec_callers.load() > 1)
-        return vec_knn_coalesced(ctx, vec_field_id, Q, n_q, k, dist_out, label_out, n_out);
+    if (mem_q == TSGPU_MEM_HOST && mem_out == TSGPU_MEM_HOST && n_q <= ctx->batch_max_queries && ctx->vec_callers.load() > 1 && (!n_excluded || excluded_ids)) {
+        if (!allow_ids && !n_excluded) return vec_knn_coalesced(ctx, vec_field_id, Q, n_q, k, nullptr, dist_out, label_out, n_out);
+        const std::vector<tsgpu_vec_filter> fl(n_q, tsgpu_vec_filter{allow_ids ? 1u : 0u, allow_ids ? n_allow : 0u, allow_ids, n_excluded, n_excluded ? excluded_ids : nullptr});   // the call's one filter, per query
+        return vec_knn_coalesced(ctx, vec_field_id, Q, n_q, k, fl.data(), dist_out, label_out, n_out);
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     return vec_knn_locked(ctx, vec_field_id, Q, mem_q, n_q, k, allow_ids, n_allow, excluded_ids, n_excluded, dist_out, label_out, n_out, mem_out);
+}
+
+int tsgpu_vec_knn_batch_filtered(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, const tsgpu_vec_filter* filters,
+                                 float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
+    if (!ctx || !Q || !dist_out || !label_out || !n_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_knn_batch_filtered: NULL argument");
+    if (n_q == 0) return ok();
+    if (k == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_knn_batch_filtered: k must be > 0");
+    if (k > TSGPU_MAX_TOPK) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_knn_batch_filtered: k > TSGPU_MAX_TOPK is not accelerated");
+    bool any = false;
+    if (int rc = check_filters(filters, n_q, any)) return rc;
+    if (!any) filters = nullptr;
+    // small host-to-host calls from concurrent request threads share rounds with tsgpu_vec_knn_batch's (the hybrid entry point's vector pass comes through here)
+    struct CallerCount { std::atomic<int>& c; explicit CallerCount(std::atomic<int>& x) : c(x) { c.fetch_add(1); } ~CallerCount() { c.fetch_sub(1); } } cc(ctx->vec_callers);
+    if (mem_q == TSGPU_MEM_HOST && mem_out == TSGPU_MEM_HOST && n_q <= ctx->batch_max_queries && ctx->vec_callers.load() > 1)
+        return vec_knn_coalesced(ctx, vec_field_id, Q, n_q, k, filters, dist_out, label_out, n_out);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return vec_knn_filtered_locked(ctx, vec_field_id, Q, mem_q, n_q, k, filters, dist_out, label_out, n_out, mem_out);
 }
 
 }  // extern "C"
@@ -759,6 +991,43 @@ static int vec_knn_locked(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q,
         TSGPU_HIP_TRY(hipStreamSynchronize(s));
         if (f->n_rows) knn_collect_timings(ctx);
     } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_vec_knn_batch: host allocation failed"); }
+    return ok();
+}
+
+// ctx->mu held by the caller
+static int vec_knn_filtered_locked(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, const tsgpu_vec_filter* filters,
+                                   float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
+    bool any = false;
+    if (int rc = check_filters(filters, n_q, any)) return rc;
+    if (!any) return vec_knn_locked(ctx, vec_field_id, Q, mem_q, n_q, k, nullptr, 0, nullptr, 0, dist_out, label_out, n_out, mem_out);    // the unfiltered call, as it is
+    (void)hipSetDevice(ctx->device);
+    VecField* f = get_field(ctx, vec_field_id);
+    if (!f) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_vec_knn_batch_filtered: unknown vector field");
+    hipStream_t s = ctx->stream;
+    try {
+        const float* Q_dev = nullptr;
+        int rc = stage_queries(ctx, f, Q, mem_q, n_q, &Q_dev);
+        if (rc) return rc;
+        float* d_dist = dist_out;
+        uint64_t* d_lab = label_out;
+        uint32_t* d_cnt = n_out;
+        if (mem_out != TSGPU_MEM_DEVICE) {
+            if ((rc = f->d_dist.reserve((size_t)n_q * k * 4))) return rc;
+            if ((rc = f->d_lab.reserve((size_t)n_q * k * 8))) return rc;
+            if ((rc = f->d_cnt.reserve((size_t)n_q * 4))) return rc;
+            d_dist = f->d_dist.as<float>(); d_lab = f->d_lab.as<uint64_t>(); d_cnt = f->d_cnt.as<uint32_t>();
+        }
+        if (f->n_rows == 0) {
+            TSGPU_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_q * 4, s));
+        } else if ((rc = knn_device_filtered(ctx, f, Q_dev, n_q, k, filters, d_dist, d_lab, d_cnt))) return rc;
+        if (mem_out != TSGPU_MEM_DEVICE) {
+            TSGPU_HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(label_out, d_lab, (size_t)n_q * k * 8, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(n_out, d_cnt, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
+        }
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        if (f->n_rows) knn_collect_timings(ctx);
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_vec_knn_batch_filtered: host allocation failed"); }
     return ok();
 }
 
@@ -1692,24 +1961,21 @@ int tsgpu_hybrid_search_batch(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uin
         else kw_pass();
         if (!overlap && rc_kw) return fail(rc_kw, err_kw);
         const auto t1 = std::chrono::steady_clock::now();
-        // 2) vector pass: one batched exact k-NN for the whole batch; a query with filter_by / excluded ids (the VectorFilterFunctor of
-        //    process_results_hnsw_index, src/index.cpp:3376-3445) gets its own exact k-NN restricted to its allowed ids afterwards
+        // 2) vector pass: ONE batched exact k-NN for the whole batch; a query with filter_by / excluded ids (the VectorFilterFunctor of
+        //    process_results_hnsw_index, src/index.cpp:3376-3445) carries them as its own filter of that batch (tsgpu_vec_knn_batch_filtered)
         KnnHost kh;
-        int rc = knn_to_host(ctx, vec_field_id, Q, mem_q, n_queries, k, nullptr, 0, nullptr, 0, kh);
+        kh.dist.assign((size_t)n_queries * k, 0.f);
+        kh.lab.assign((size_t)n_queries * k, 0);
+        kh.cnt.assign(n_queries, 0);
+        std::vector<tsgpu_vec_filter> vf(n_queries);
+        for (uint32_t q = 0; q < n_queries; q++) {
+            const bool fa = queries[q].n_filter != 0 && queries[q].filter_ids, fe = queries[q].n_excluded != 0 && queries[q].excluded_ids;
+            vf[q] = tsgpu_vec_filter{fa ? 1u : 0u, fa ? queries[q].n_filter : 0u, fa ? queries[q].filter_ids : nullptr, fe ? queries[q].n_excluded : 0u, fe ? queries[q].excluded_ids : nullptr};
+        }
+        int rc = tsgpu_vec_knn_batch_filtered(ctx, vec_field_id, Q, mem_q, n_queries, k, vf.data(), kh.dist.data(), kh.lab.data(), kh.cnt.data(), TSGPU_MEM_HOST);
         if (kw_thread.joinable()) kw_thread.join();
         if (rc_kw) return fail(rc_kw, err_kw);
         if (rc) return rc;
-        {
-            KnnHost one;
-            for (uint32_t q = 0; q < n_queries; q++) {
-                if (st[q] != TSGPU_OK || (queries[q].n_excluded == 0 && queries[q].n_filter == 0)) continue;
-                if ((rc = knn_to_host(ctx, vec_field_id, Q + (size_t)q * f->dim, mem_q, 1, k, queries[q].n_filter ? queries[q].filter_ids : nullptr, queries[q].n_filter,
-                                      queries[q].n_excluded ? queries[q].excluded_ids : nullptr, queries[q].n_excluded, one))) return rc;
-                std::copy(one.dist.begin(), one.dist.end(), kh.dist.begin() + (size_t)q * k);
-                std::copy(one.lab.begin(), one.lab.end(), kh.lab.begin() + (size_t)q * k);
-                kh.cnt[q] = one.cnt[0];
-            }
-        }
         const auto t2 = std::chrono::steady_clock::now();
         // 3) fusion on the host, exactly as the reference
         rc = tsgpu_hybrid_fuse_batch(ctx, queries, p, f->metric, &kw, kh.dist.data(), kh.lab.data(), kh.cnt.data(), k, n_queries, out);

@@ -53,6 +53,93 @@ __device__ inline float ord_f32(uint32_t o) {
     return __uint_as_float(b);
 }
 
+// ------------------------------------------------------------------------------------------------
+// PER-QUERY ROW MASKS (tsgpu_vec_knn_batch_filtered): every query of a batch has its own allowed set, one pass over the rows serves them all.
+// A filtered query owns one bitmap of 4 * n_tiles 32-bit words (whole 128-row tiles: a tile's four words always exist); bit r = row r is live,
+// allowed and not excluded. off[q] = index of the query's bitmap, VEC_QMASK_NONE = the query has no filter and keeps the shared row_ok test.
+// The scan kernels take the masks behind a template parameter (PQ): the instantiations an unfiltered batch launches are the code they were.
+// A lane's 16 accumulator rows of one (rb, cb) block are rows g0 + 4 * (lane >> 5) + (el & 3) + 8 * (el >> 2) of the 32-aligned group
+// g0 = r0 + 64 * strip + 32 * rb: ONE word load per (rb, cb) and lane decides all of them.
+// Out of scope here: per-query masks in vec_hnsw_search_kernel, a per-query parameter block for tsgpu_vector_search_batch, the
+// tsgpu_group_* shard forms (they keep their per-query loop), filters that already live on the device.
+static const uint32_t VEC_QMASK_NONE = 0xFFFFFFFFu;
+struct VecQMasks {
+    const uint32_t* bits;      // [n_maps][words]
+    const uint32_t* off;       // [n_q]
+    uint32_t words;            // 4 * n_tiles
+};
+// the 32-row group's word of query gq (rows of the group that pass); `none` = the query has no bitmap
+__device__ inline const uint32_t* vec_qmask_of(const VecQMasks& m, uint32_t gq, uint32_t n_q) {
+    const uint32_t o = gq < n_q ? m.off[gq] : VEC_QMASK_NONE;
+    return o == VEC_QMASK_NONE ? nullptr : m.bits + (size_t)o * m.words;
+}
+
+// The id lists of a group's filtered queries as ROWS, CSR per list: sorted ascending; duplicates and rows >= n_rows are allowed and ignored.
+struct VecFilterLists {
+    const uint32_t* rows;          // both kinds of list, addressed through the two offset arrays
+    const uint64_t* allow_ptr;     // [n + 1]
+    const uint64_t* excl_ptr;      // [n + 1]
+    const uint8_t* filtered;       // [n] 1 = only the allow rows pass, 0 = every live row
+};
+__device__ inline uint64_t vec_rows_lower_bound(const uint32_t* __restrict__ a, uint64_t lo, uint64_t hi, uint32_t v) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// bits of the rows of list [lo, hi) that fall into [r0, r0 + 32)
+__device__ inline uint32_t vec_rows_word(const uint32_t* __restrict__ a, uint64_t lo, uint64_t hi, uint32_t r0) {
+    uint32_t w = 0;
+    for (uint64_t j = vec_rows_lower_bound(a, lo, hi, r0); j < hi; j++) {
+        const uint32_t d = a[j] - r0;
+        if (d >= 32u) break;
+        w |= 1u << d;
+    }
+    return w;
+}
+// One thread per OUTPUT WORD (no atomics, no memset): pack the 32 row_ok bytes, AND in the allow rows of the range, AND out the excluded ones.
+__global__ __launch_bounds__(256) void vec_qmask_build_kernel(VecFilterLists L, const uint8_t* __restrict__ row_ok, uint32_t n_rows, uint32_t words, uint32_t n_maps,
+                                                               uint32_t* __restrict__ bits) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)n_maps * words) return;
+    const uint32_t m = (uint32_t)(i / words), r0 = (uint32_t)(i % words) * 32u;
+    uint32_t v = 0;
+    if (r0 < n_rows) {
+        const uint32_t n = n_rows - r0 < 32u ? n_rows - r0 : 32u;
+        if (row_ok) { for (uint32_t b = 0; b < n; b++) v |= (row_ok[r0 + b] != 0 ? 1u : 0u) << b; }
+        else v = n == 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
+        if (L.filtered[m]) v &= vec_rows_word(L.rows, L.allow_ptr[m], L.allow_ptr[m + 1], r0);
+        v &= ~vec_rows_word(L.rows, L.excl_ptr[m], L.excl_ptr[m + 1], r0);
+    }
+    bits[i] = v;
+}
+// Short allow lists skip the scan: the live, not excluded rows of list q go straight into the survivor arena (surv_cnt zeroed by the host; the
+// order inside a list is free, the exact keys decide). One workgroup per list.
+__global__ __launch_bounds__(256) void vec_direct_fill_kernel(VecFilterLists L, const uint8_t* __restrict__ row_ok, uint32_t n_rows, uint32_t* __restrict__ surv,
+                                                               size_t stride, uint32_t* __restrict__ surv_cnt) {
+    const uint32_t q = blockIdx.x;
+    const uint64_t a0 = L.allow_ptr[q], a1 = L.allow_ptr[q + 1], e0 = L.excl_ptr[q], e1 = L.excl_ptr[q + 1];
+    for (uint64_t j = a0 + threadIdx.x; j < a1; j += 256) {
+        const uint32_t row = L.rows[j];
+        if (row >= n_rows || (j > a0 && L.rows[j - 1] == row)) continue;
+        if (row_ok && row_ok[row] == 0) continue;
+        const uint64_t e = vec_rows_lower_bound(L.rows, e0, e1, row);
+        if (e < e1 && L.rows[e] == row) continue;
+        const uint32_t slot = atomicAdd(&surv_cnt[q], 1u);
+        if (slot < stride) surv[(size_t)q * stride + slot] = row;
+    }
+}
+// rows of a [n][width] array gathered / scattered through a permutation: dst[i] = src[perm[i]] (scatter == 0) or dst[perm[i]] = src[i]
+template <class Tp>
+__global__ __launch_bounds__(256) void vec_permute_rows_kernel(const Tp* __restrict__ src, Tp* __restrict__ dst, const uint32_t* __restrict__ perm, uint32_t n, uint32_t width,
+                                                                int scatter) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)n * width) return;
+    const uint32_t r = (uint32_t)(i / width), c = (uint32_t)(i % width);
+    if (scatter) dst[(size_t)perm[r] * width + c] = src[i]; else dst[i] = src[(size_t)perm[r] * width + c];
+}
+
 struct VecScanArgs {
     const float* X;            // [n_rows][dim] row-major
     const uint8_t* row_ok;     // nullable: 0 = skip row (deleted / filtered out)
@@ -69,6 +156,7 @@ struct VecScanArgs {
     uint32_t cand_cap;
     uint64_t* dense;           // dense mode (non-null): dense[q * dense_stride + ordinal*128 + r] = key or INF
     uint32_t dense_stride;
+    VecQMasks qm;              // PQ instantiations only: per-query row bitmaps
 };
 
 template <int QT>
@@ -77,8 +165,8 @@ struct VecScanSmem {
     alignas(16) float qs[2][QT * VEC_LDW];
 };
 
-// CB = 32-query column blocks per wave (QT = 64 * CB); ALIGNED = dim % 4 == 0 and 16-byte aligned bases
-template <int CB, bool ALIGNED>
+// CB = 32-query column blocks per wave (QT = 64 * CB); ALIGNED = dim % 4 == 0 and 16-byte aligned bases; PQ = per-query row bitmaps (a.qm)
+template <int CB, bool ALIGNED, bool PQ = false>
 __global__ __launch_bounds__(VEC_THREADS, 2) void vec_scan_kernel(VecScanArgs a) {
     constexpr int QT = 64 * CB;
     constexpr int XV = VEC_ROWS * VEC_KC / 4 / VEC_THREADS;     // float4 per thread per X chunk (4)
@@ -245,20 +333,26 @@ __global__ __launch_bounds__(VEC_THREADS, 2) void vec_scan_kernel(VecScanArgs a)
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 const uint32_t gq = q0 + wcol + cb * 32 + (lane & 31);
+                const uint32_t* qmw = nullptr;                  // PQ: this query's bitmap words of the tile (null = it has none)
+                if constexpr (PQ) { qmw = vec_qmask_of(a.qm, gq, a.n_q); if (qmw) qmw += (r0 + wrow) >> 5; }
                 if (a.dense) {
                     if (gq < a.n_q) {
 #pragma unroll
-                        for (int rb = 0; rb < 2; rb++)
+                        for (int rb = 0; rb < 2; rb++) {
+                            uint32_t mbits = 0;
+                            if constexpr (PQ) { if (qmw) mbits = qmw[rb] >> (4 * (lane >> 5)); }
 #pragma unroll
                             for (int e = 0; e < 16; e++) {
                                 const uint32_t lr = wrow + rb * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                                 const uint32_t row = r0 + lr;
                                 bool okr = row < a.n_rows;
-                                if (okr && a.row_ok) okr = a.row_ok[row] != 0;
+                                if (PQ && qmw) okr = okr && ((mbits >> ((e & 3) + 8 * (e >> 2))) & 1u) != 0;
+                                else if (okr && a.row_ok) okr = a.row_ok[row] != 0;
                                 const float dist = 1.0f - acc[rb][cb][e];
                                 a.dense[(size_t)gq * a.dense_stride + (size_t)(o * VEC_ROWS + lr)] =
                                     okr ? (((uint64_t)f32_ord(dist) << 32) | row) : VEC_KEY_INF;
                             }
+                        }
                     }
                 } else {
                     // cheap reject: the best (largest) dot of this lane's 32 scores for the column
@@ -269,17 +363,21 @@ __global__ __launch_bounds__(VEC_THREADS, 2) void vec_scan_kernel(VecScanArgs a)
                         for (int e = 0; e < 16; e++) amax = fmaxf(amax, acc[rb][cb][e]);
                     if (gq < a.n_q && !((1.0f - amax) > tau_dist[cb])) {     // NaN-safe: NaN never rejects here
 #pragma unroll
-                        for (int rb = 0; rb < 2; rb++)
+                        for (int rb = 0; rb < 2; rb++) {
+                            uint32_t mbits = 0;
+                            if constexpr (PQ) { if (qmw) mbits = qmw[rb] >> (4 * (lane >> 5)); }     // (behind the amax test)
 #pragma unroll
                             for (int e = 0; e < 16; e++) {
                                 const uint32_t row = r0 + wrow + rb * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                                 const float dist = 1.0f - acc[rb][cb][e];
                                 const uint64_t key = ((uint64_t)f32_ord(dist) << 32) | row;
-                                if (key <= tau_key[cb] && row < a.n_rows && (!a.row_ok || a.row_ok[row] != 0)) {
+                                if (key <= tau_key[cb] && row < a.n_rows &&
+                                    ((PQ && qmw) ? ((mbits >> ((e & 3) + 8 * (e >> 2))) & 1u) != 0 : (!a.row_ok || a.row_ok[row] != 0))) {
                                     const uint32_t slot = atomicAdd(&a.cand_cnt[gq], 1u);
                                     if (slot < a.cand_cap) a.cand[(size_t)gq * a.cand_cap + slot] = key;
                                 }
                             }
+                        }
                     }
                 }
             }
@@ -545,6 +643,7 @@ struct VecHScanArgs {
     // (g = 64-row strip * 2 + half) of the ordinal-th sampled tile; 0xFFFFFFFF = no valid row in the group
     uint32_t* gmax;
     uint32_t gstride;
+    VecQMasks qm;              // PQ instantiations only: per-query row bitmaps
 };
 
 // 16 bytes per lane straight from global memory into LDS (LDS-DMA, global_load_lds_dwordx4): the destination is
@@ -612,7 +711,9 @@ struct VecHScanSmem {
 
 // (round 4's int8 mirror — v_mfma_i32_32x32x32_i8 over per-tile quantised rows: the scan itself 3.1 ms instead of 4.4, but its wider bracket sent 3-4x the rows
 //  to the exact re-score, a net loss end to end; profiles/r04/exp_vec_int8.txt — was removed in round 6)
-template <int CB>
+// PQ = per-query row bitmaps (a.qm; "PER-QUERY ROW MASKS" above): the same mask in the sample pass and in the scan, so L1 is a bound over the
+// query's ALLOWED rows only (a query whose sample holds fewer than k allowed rows gets L1 = -inf and keeps every allowed row)
+template <int CB, bool PQ = false>
 __global__ __launch_bounds__(VEC_HTHREADS) void vec_hscan_kernel(VecHScanArgs a) {
     constexpr int QT = 64 * CB;
     constexpr int BK = CB >= 4 ? 32 : 64;              // k per step
@@ -820,6 +921,8 @@ __global__ __launch_bounds__(VEC_HTHREADS) void vec_hscan_kernel(VecHScanArgs a)
                     const uint32_t col = wcol + cb * 32 + (lane & 31);
                     const uint32_t gq = q0 + col;
                     const float e = cqv[cb] * nmax + 1e-30f;             // >= every row's error radius in this tile
+                    const uint32_t* qmw = nullptr;                       // PQ: this query's bitmap words of the strip (null = it has none)
+                    if constexpr (PQ) { qmw = vec_qmask_of(a.qm, gq, a.n_q); if (qmw) qmw += (r0 + strip * 64) >> 5; }
                     if (a.mode == 0) {
                         // keep a row iff its upper bound reaches T = L1[q] (= T(L1), distance space): !(sc + e < T), tested as !(sc < thr),
                         // thr = fl(T - e). Sound whatever that subtraction rounds to, also where e << ulp(T) (the distance-tie regime): rounding
@@ -838,7 +941,9 @@ __global__ __launch_bounds__(VEC_HTHREADS) void vec_hscan_kernel(VecHScanArgs a)
                             // a group that holds a candidate for some lane is walked)
                             uint64_t* __restrict__ seg = a.seg + ((size_t)slab * a.n_q + gq) * a.seg_cap;
 #pragma unroll
-                            for (int rb = 0; rb < 2; rb++)
+                            for (int rb = 0; rb < 2; rb++) {
+                                uint32_t mbits = 0;                                                 // (one word per (rb, cb), behind the amax test)
+                                if constexpr (PQ) { if (qmw) mbits = qmw[rb] >> (4 * (lane >> 5)); }
 #pragma unroll
                                 for (int g4 = 0; g4 < 4; g4++) {
                                     const float gm = fmaxf(fmaxf(acc[rb][cb][4 * g4], acc[rb][cb][4 * g4 + 1]), fmaxf(acc[rb][cb][4 * g4 + 2], acc[rb][cb][4 * g4 + 3]));
@@ -848,27 +953,33 @@ __global__ __launch_bounds__(VEC_HTHREADS) void vec_hscan_kernel(VecHScanArgs a)
                                         const int el = 4 * g4 + e4;
                                         const uint32_t row = rbase + rb * 32 + (el & 3) + 8 * (el >> 2);
                                         const float sc = acc[rb][cb][el];
-                                        if (!(sc < thr) && row < a.n_rows && (!a.row_ok || a.row_ok[row] != 0)) {
+                                        if (!(sc < thr) && row < a.n_rows &&
+                                            ((PQ && qmw) ? ((mbits >> ((el & 3) + 8 * (el >> 2))) & 1u) != 0 : (!a.row_ok || a.row_ok[row] != 0))) {
                                             const uint32_t slot = atomicAdd(&sm.cnt[col], 1u);      // LDS
                                             if (slot < a.seg_cap) seg[slot] = ((uint64_t)__float_as_uint(sc) << 32) | row;
                                         }
                                     }
                                 }
+                            }
                         }
                     } else if (gq < a.n_q) {
                         // sample pass: one key per (query, 32-row group) — the group's best lower bound. The k-th largest of
                         // these maxima is a valid lower bound of the k-th best score (k groups -> k distinct rows).
                         float best = __uint_as_float(0xFF800000u);
 #pragma unroll
-                        for (int rb = 0; rb < 2; rb++)
+                        for (int rb = 0; rb < 2; rb++) {
+                            uint32_t mbits = 0;
+                            if constexpr (PQ) { if (qmw) mbits = qmw[rb] >> (4 * (lane >> 5)); }
 #pragma unroll
                             for (int el = 0; el < 16; el++) {
                                 const uint32_t row = rbase + rb * 32 + (el & 3) + 8 * (el >> 2);
                                 bool okr = row < a.n_rows;
-                                if (okr && a.row_ok) okr = a.row_ok[row] != 0;
+                                if (PQ && qmw) okr = okr && ((mbits >> ((el & 3) + 8 * (el >> 2))) & 1u) != 0;      // a filtered-out row must not feed L1
+                                else if (okr && a.row_ok) okr = a.row_ok[row] != 0;
                                 const float lb = acc[rb][cb][el] - e;
                                 if (okr && f32_finite(lb) && lb > best) best = lb;
                             }
+                        }
                         a.gmax[(size_t)gq * a.gstride + (size_t)o * 4 + strip * 2 + (lane >> 5)] = f32_finite(best) ? f32_desc_key(best) : 0xFFFFFFFFu;
                     }
                 }

@@ -540,6 +540,33 @@ class GpuIndex:
                                             _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
         return dist, lab, cnt
 
+    def vec_knn_batch_filtered(self, field_id, Q, k, filters):
+        """tsgpu_vec_knn_batch_filtered: one exact k-NN batch in which query i has its own filter. filters: None (no query is filtered) or one entry
+        per query: None (no filter) or (allow_ids | None, excluded_ids | None); sorted seq_ids; an EMPTY allow list allows nothing"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
+        n = Q.shape[0]
+        dist = np.zeros((n, k), np.float32)
+        lab = np.zeros((n, k), np.uint64)
+        cnt = np.zeros(n, np.uint32)
+        arr, keep = None, []
+        if filters is not None:
+            assert len(filters) == n
+            arr = (B.VecFilterC * max(n, 1))()
+            for i, f in enumerate(filters):
+                if f is None:
+                    continue
+                allow, excl = f
+                if allow is not None:
+                    a = _u32(allow)
+                    keep.append(a)
+                    arr[i].filtered, arr[i].n_allow, arr[i].allow_ids = 1, a.size, a.ctypes.data if a.size else None
+                if excl is not None:
+                    e = _u32(excl)
+                    keep.append(e)
+                    arr[i].n_excluded, arr[i].excluded_ids = e.size, e.ctypes.data if e.size else None
+        self._ck(self.L.tsgpu_vec_knn_batch_filtered(self.h, field_id, _vp(Q), B.MEM_HOST, n, k, arr, _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
+        return dist, lab, cnt
+
     def vec_knn_batch_raw(self, field_id, q_ptr, mem_q, n, k, dist_ptr, lab_ptr, cnt_ptr, mem_out):
         self._ck(self.L.tsgpu_vec_knn_batch(self.h, field_id, C.c_void_p(q_ptr), mem_q, n, k, None, 0, None, 0,
                                             C.c_void_p(dist_ptr), C.c_void_p(lab_ptr), C.c_void_p(cnt_ptr), mem_out))
