@@ -531,8 +531,9 @@ int tsgpu_vec_knn_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, i
  * serves the whole batch. Query i answers exactly as tsgpu_vec_knn_batch does for Q[i] alone with filters[i] (order, tie rule, distance bits,
  * n_out); deleted rows are never returned, unknown labels in a list are ignored. Allow lists of at most "vec_filter_direct_max" ids are
  * re-scored directly, the other queries share one masked scan. Small host-to-host calls from concurrent threads are coalesced exactly like
- * tsgpu_vec_knn_batch's, and with them ("batch_max_queries"); tsgpu_hybrid_search_batch's vector pass is such a call. Not covered (they keep one pass per filtered query): the HNSW search, tsgpu_vector_search_batch's single parameter block, the
- * tsgpu_group_* shard forms; filters must be host lists. */
+ * tsgpu_vec_knn_batch's, and with them ("batch_max_queries"); tsgpu_hybrid_search_batch's vector pass is such a call. The HNSW search takes the same
+ * filters (tsgpu_vec_hnsw_search_batch_filtered). Not covered (they keep one pass per filtered query): tsgpu_vector_search_batch's single parameter
+ * block, the tsgpu_group_* shard forms; filters must be host lists. */
 typedef struct tsgpu_vec_filter {
     uint32_t filtered;              /* 0 = no allow list (all live rows); 1 = only allow_ids (n_allow == 0: nothing) */
     uint32_t n_allow;
@@ -598,6 +599,20 @@ int tsgpu_vec_hnsw_export(tsgpu_ctx* ctx, uint32_t vec_field_id, int32_t info[4]
 int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
                                 int functor_present, const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids,
                                 uint32_t n_excluded, float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out);
+/* The same search with ONE FILTER PER QUERY (the server's calling convention: every request brings its own filter_by): filters[i] restricts query i
+ * only, NULL = no query is filtered; if no filter restricts, the call IS tsgpu_vec_hnsw_search_batch without lists. Query i answers exactly as
+ * tsgpu_vec_hnsw_search_batch does for Q[i] alone with filters[i] (labels, order, distance bits, n_out, the 0xFFFFFFFF status); functor_present is the
+ * batch's. A restricting query owns a row bitmap (the exact path's, built on the device from its lists), the traversal tests one bit of ITS map where
+ * it tested the shared mask: ONE launch serves the batch, re-runs included (a batch whose maps exceed 4 GiB is split into consecutive groups of
+ * queries, one launch each). Counters "hnsw_launches" (traversal launches so far, re-runs included) and "hnsw_filter_maps" (bitmaps built so far).
+ * Both HNSW entry points COALESCE: a host-to-host call of at most "batch_max_queries" queries made while another thread is inside either of them
+ * parks, and the parked calls of one (field, k, ef, functor_present) run as one filtered batch — the old entry point's single filter replicated per
+ * query (host/tsgpu_hnsw_adaptor.h's one-query calls gain by this). These rounds are counted apart from the k-NN and keyword rounds:
+ * "hnsw_batch_rounds" / "hnsw_batch_coalesced_calls"; a lone caller takes the direct path. After a coalesced call "hnsw_last_expansions" /
+ * "hnsw_last_distances" describe the ROUND the call ran in, not the call. */
+int tsgpu_vec_hnsw_search_batch_filtered(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
+                                         int functor_present, const tsgpu_vec_filter* filters, float* dist_out, uint64_t* label_out,
+                                         uint32_t* n_out, int mem_out);
 
 /* distances of one query to explicit labels (flat scan over filter ids, src/index.cpp:3345-3374);
  * missing labels get NaN (the reference `continue`s on the throw). Host pointers. */

@@ -1,0 +1,51 @@
+"""`-m gpu` twin of tests/test_emu_hnsw_filters.py: per-query filters in one HNSW search batch and the coalescer of small HNSW calls (bodies and what
+they compare: tests/hnsw_filters_common.py) through libtsgpu.so on a real MI355X. The mixed batch runs its full 24 queries here."""
+import pytest
+
+from typesense_amd import _lib as B
+from tests import helpers as H
+from tests import hnsw_filters_common as V
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def _real_library(monkeypatch):
+    """a guard: the bodies take the library path as an argument; should a helper they import ever ask for the emulator build, it gets the real library"""
+    monkeypatch.setattr(H, "emu_lib_path", lambda *a, **k: H.gpu_lib_path())
+
+
+@pytest.mark.parametrize("k,ef", V.MIXED_K_EF)
+@pytest.mark.parametrize("metric", [B.METRIC_IP, B.METRIC_COSINE])
+def test_mixed_filters_in_one_batch_match_the_oracle_and_the_single_filter_call(metric, k, ef):
+    V.body_mixed_batch(H.gpu_lib_path(), metric, k, ef)
+
+
+@pytest.mark.parametrize("k,ef", V.MIXED_K_EF)
+def test_the_batch_is_one_launch_and_the_same_traversal(k, ef):
+    V.body_one_launch_same_traversal(H.gpu_lib_path(), B.METRIC_IP, k, ef)
+
+
+def test_a_batch_whose_maps_do_not_fit_is_split_into_groups():
+    V.body_group_split(H.gpu_lib_path(), B.METRIC_IP, 10, 64)
+
+
+@pytest.mark.parametrize("n,label_base", [(129, 0), (33, 0), (200, 1000)])
+def test_small_and_ragged_shapes(n, label_base):
+    V.body_small_shape(H.gpu_lib_path(), n, label_base)
+
+
+def test_masks_follow_a_query_through_the_rerun_ladder():
+    V.body_masks_through_the_rerun_ladder(H.gpu_lib_path())
+
+
+def test_a_block_serves_queries_with_different_maps_in_turn():
+    V.body_several_queries_per_block(H.gpu_lib_path())
+
+
+def test_one_query_calls_from_8_threads_coalesce_across_both_entry_points():
+    V.body_calls_coalesce(H.gpu_lib_path())
+
+
+def test_arguments():
+    V.body_arguments(H.gpu_lib_path())

@@ -391,6 +391,7 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "hnsw_visited_hash")) { ctx->hnsw_visited_hash = value != 0; return ok(); }
     if (!strcmp(name, "hnsw_test_tiny_cand")) { ctx->hnsw_test_tiny_cand = value != 0; return ok(); }
     if (!strcmp(name, "hnsw_test_slots")) { ctx->hnsw_test_slots = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 4096); return ok(); }
+    if (!strcmp(name, "hnsw_test_max_maps")) { ctx->hnsw_test_max_maps = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return ok(); }
     if (!strcmp(name, "hnsw_test_epoch")) { ctx->hnsw_test_epoch = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 0xFFFF); return ok(); }
     if (!strcmp(name, "hnsw_visited_max_gib")) { ctx->hnsw_visited_max_gib = (int)std::min<int64_t>(std::max<int64_t>(1, value), 128); return ok(); }
     if (!strcmp(name, "blocking_sync_min_callers")) { ctx->blocking_sync_min_callers = (int)std::max<int64_t>(0, value); return ok(); }
@@ -480,6 +481,10 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "vec_candidate_rows")) { *out = ctx->vec_candidate_rows; return ok(); }
     if (!strcmp(name, "hnsw_last_expansions")) { *out = ctx->hnsw_last_expansions; return ok(); }
     if (!strcmp(name, "hnsw_tier_reruns")) { *out = ctx->hnsw_tier_reruns; return ok(); }
+    if (!strcmp(name, "hnsw_launches")) { *out = ctx->hnsw_launches; return ok(); }
+    if (!strcmp(name, "hnsw_filter_maps")) { *out = ctx->hnsw_filter_maps; return ok(); }
+    if (!strcmp(name, "hnsw_batch_rounds")) { *out = ctx->hnsw_comb.rounds; return ok(); }                       // coalesced HNSW rounds (not part of batch_rounds)
+    if (!strcmp(name, "hnsw_batch_coalesced_calls")) { *out = ctx->hnsw_comb.coalesced_calls; return ok(); }     // calls served by those rounds
     if (!strcmp(name, "hnsw_last_distances")) { *out = ctx->hnsw_last_distances; return ok(); }
     if (!strcmp(name, "commit_last_us")) { *out = ctx->commit_last_us; return ok(); }                        // the last tsgpu_commit: wall time, bytes uploaded
     if (!strcmp(name, "commit_last_uploaded_bytes")) { *out = ctx->commit_last_uploaded_bytes; return ok(); }

@@ -380,6 +380,7 @@ struct KwRequest;                                    // tsgpu.hip
 struct GroupByScratch;                               // tsgpu_groupby.inc.h
 struct GbRequest;                                    // tsgpu_groupby.inc.h
 struct VecRequest;                                   // tsgpu_vec.hip
+struct HnswRequest;                                  // tsgpu_vec.hip
 
 }  // namespace tsgpu
 
@@ -520,7 +521,8 @@ struct tsgpu_ctx {
     tsgpu::Combiner<tsgpu::KwRequest> kw_comb;
     tsgpu::Combiner<tsgpu::VecRequest> vec_comb;
     tsgpu::Combiner<tsgpu::GbRequest> gb_comb;       // grouped keyword calls (tsgpu_keyword_search_grouped_batch)
-    std::atomic<int> kw_callers{0}, vec_callers{0}, gb_callers{0};  // threads currently inside the search entry points
+    tsgpu::Combiner<tsgpu::HnswRequest> hnsw_comb;   // small HNSW searches (both tsgpu_vec_hnsw_search_batch entry points): rounds and counters of their own
+    std::atomic<int> kw_callers{0}, vec_callers{0}, gb_callers{0}, hnsw_callers{0};  // threads currently inside the search entry points
     uint32_t ticks_per_us = 100;                     // device wall clock (hipDeviceAttributeWallClockRate)
     bool hybrid_overlap = true;                      // tsgpu_hybrid_search_batch: keyword pass and vector pass at the same time (option "hybrid_overlap")
     uint32_t facet_ids_per_block = 0;      // 0 = chosen per batch (tsgpu_facet_count_batch)
@@ -591,6 +593,10 @@ struct tsgpu_ctx {
                                                      // otherwise), in both visited modes, so that a block serves several queries in a batch of a few
     uint32_t hnsw_test_epoch = 0;                    // TESTS ONLY (option "hnsw_test_epoch"): when non-zero, the next tag-mode launch starts from this tag epoch, once (the
                                                      // clear of the tags at epoch 0xFFF0 is reached without 65 000 queries per slot)
+    uint32_t hnsw_test_max_maps = 0;                 // TESTS ONLY (option "hnsw_test_max_maps"): when non-zero, caps the per-query bitmaps of ONE launch of a filtered HNSW batch (the
+                                                     // 4 GiB arena bound otherwise), so that the split into consecutive query groups is exercised on a few queries
+    uint64_t hnsw_launches = 0;                      // traversal kernel launches since the context was created, re-runs included (counter "hnsw_launches")
+    uint64_t hnsw_filter_maps = 0;                   // per-query bitmaps built for filtered HNSW batches (counter "hnsw_filter_maps")
     uint64_t hnsw_tier_reruns = 0;                   // queries that were run again on the largest tier since the context was created (counter "hnsw_tier_reruns")
     int hnsw_visited_hash = 1;                        // 1 = per-query hash sets of visited ids (default), 0 = 16-bit tags per row and concurrent query
     int hnsw_visited_max_gib = 64;                    // cap of one field's HNSW visited-tag array (option): bounds the queries traversing concurrently
@@ -598,7 +604,7 @@ struct tsgpu_ctx {
     int plan_threads = 8;                             // host threads that plan a big keyword batch in slices ("plan_threads")
     uint32_t plan_parallel_min_queries = 2048;        // ... from this many queries on (0 = never; "plan_parallel_min_queries")
     int fuse_threads = 32;                            // host threads of the hybrid rank fusion (option "fuse_threads")
-    uint64_t hnsw_last_expansions = 0, hnsw_last_distances = 0;   // last HNSW batch: candidates expanded / distances computed at layer 0 (all queries)
+    uint64_t hnsw_last_expansions = 0, hnsw_last_distances = 0;   // last HNSW batch (of a coalesced call: its round): candidates expanded / distances computed at layer 0 (all queries)
     uint64_t vec_rescored_rows = 0;                  // survivors re-scored in fp32 by the last prefilter group (sum over its queries; 0 unless vec_count_rescored)
     uint64_t vec_candidate_rows = 0;                 // rows past the tile-level bound in that group's last scan round (sum over slabs and queries; same switch)
     uint32_t vec_count_rescored = 0;

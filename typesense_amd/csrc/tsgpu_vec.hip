@@ -453,6 +453,50 @@ static int upload_filter_lists(tsgpu_ctx* ctx, VecField* f, const tsgpu_vec_filt
 
 static bool filter_restricts(const tsgpu_vec_filter& fl) { return fl.filtered || fl.n_excluded; }
 
+// The row bitmaps of ONE GROUP of a filtered batch, for the exact scan and the HNSW traversal alike. The group starts at query g0 of a run of n queries
+// (query i of the run is filters[order ? order[i] : i]) and takes up to max_queries of them, of which at most max_maps own a bitmap: as many as the
+// 4 GiB arena holds, fewer if maps_cap (non-zero) says so. A restricting query owns one bitmap of 4 words per 128-row tile (vec_qmask_build_kernel folds
+// row_ok, its allow rows and its excluded rows into it), the others get off[] = VEC_QMASK_NONE. -> g1 (the group's end), n_maps, qm (bits / off in
+// f->d_qbits / f->d_qoff, off[] indexed from g0; untouched pointers when no query of the group restricts). Caller holds ctx->mu.
+static int build_group_masks(tsgpu_ctx* ctx, VecField* f, const tsgpu_vec_filter* filters, const uint32_t* order, uint32_t g0, uint32_t n, uint32_t max_queries,
+                             uint32_t maps_cap, uint32_t& g1, uint32_t& n_maps, VecQMasks& qm) {
+    hipStream_t s = ctx->stream;
+    const uint32_t n_rows = (uint32_t)f->n_rows;
+    const uint32_t words = 4 * ((n_rows + VEC_ROWS - 1) / VEC_ROWS);
+    const uint64_t map_bytes = (uint64_t)words * 4, arena_limit = 4ull << 30;
+    uint32_t max_maps = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(0xFFFFFFF0u, arena_limit / std::max<uint64_t>(map_bytes, 1)));
+    if (maps_cap) max_maps = std::min(max_maps, maps_cap);
+    const bool timed = ctx->vec_count_rescored != 0;
+    auto now_us = []() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    std::vector<uint32_t> owners, qoff;
+    g1 = g0; n_maps = 0;
+    while (g1 < n && g1 - g0 < max_queries) {
+        const uint32_t q = order ? order[g1] : g1;
+        const bool own = filter_restricts(filters[q]);
+        if (own && n_maps == max_maps) break;
+        qoff.push_back(own ? n_maps : VEC_QMASK_NONE);
+        if (own) { owners.push_back(q); n_maps++; }
+        g1++;
+    }
+    qm = VecQMasks{nullptr, nullptr, words};
+    if (!n_maps) return TSGPU_OK;
+    int rc;
+    const uint32_t nq = g1 - g0;
+    const uint64_t t0 = timed ? now_us() : 0;
+    VecFilterLists L;
+    if ((rc = upload_filter_lists(ctx, f, filters, owners.data(), n_maps, L))) return rc;
+    const uint64_t t1 = timed ? now_us() : 0;
+    if ((rc = f->d_qbits.reserve((size_t)n_maps * map_bytes)) || (rc = f->d_qoff.reserve((size_t)nq * 4))) return rc;
+    TSGPU_HIP_TRY(hipMemcpyAsync(f->d_qoff.p, qoff.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(vec_qmask_build_kernel, dim3((uint32_t)(((uint64_t)n_maps * words + 255) / 256)), dim3(256), 0, s, L, f->row_ok.as<uint8_t>(), n_rows, words, n_maps,
+                       f->d_qbits.as<uint32_t>());
+    TSGPU_HIP_TRY(hipGetLastError());
+    TSGPU_HIP_TRY(hipStreamSynchronize(s));                 // qoff's staging vector dies with this frame
+    if (timed) { ctx->vec_filter_stage_us += t1 - t0; ctx->vec_filter_build_us += now_us() - t1; }
+    qm.bits = f->d_qbits.as<uint32_t>(); qm.off = f->d_qoff.as<uint32_t>();
+    return TSGPU_OK;
+}
+
 // Exact k-NN of n_q queries with one filter each; Q_dev as knn_device takes it, outputs [n_q][k] on the device in caller order. Caller holds ctx->mu.
 //   direct queries  allow list of <= vec_filter_direct_max ids (bracket path only: its exact re-score is what they run on): vec_direct_fill_kernel writes
 //                   their live, not excluded rows into the survivor arena, vec_rescore_kernel + vec_select_kernel finish — no scan;
@@ -464,9 +508,6 @@ static int knn_device_filtered(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
     hipStream_t s = ctx->stream;
     const uint32_t GROUP = 512;
     const uint32_t n_rows = (uint32_t)f->n_rows;
-    const uint32_t n_tiles = (n_rows + VEC_ROWS - 1) / VEC_ROWS;
-    const uint32_t words = 4 * n_tiles;
-    const uint64_t arena_limit = 4ull << 30;
     const uint8_t* shared_mask = f->any_deleted ? f->row_ok.as<uint8_t>() : nullptr;
     const uint32_t direct_max = ctx->vec_prefilter ? ctx->vec_filter_direct_max : 0;
     std::vector<uint32_t> perm, direct;
@@ -494,37 +535,14 @@ static int knn_device_filtered(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, 
     const bool timed = ctx->vec_count_rescored != 0;
     auto now_us = []() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     // ---- scan queries
-    const uint64_t map_bytes = (uint64_t)words * 4;
-    const uint32_t max_maps = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(GROUP, arena_limit / std::max<uint64_t>(map_bytes, 1)));
     bool first = true;
     for (uint32_t g0 = 0; g0 < n_scan;) {
-        // the group: up to GROUP queries, of which at most max_maps own a bitmap
-        uint32_t g1 = g0, n_maps = 0;
-        std::vector<uint32_t> owners, qoff;
-        while (g1 < n_scan && g1 - g0 < GROUP) {
-            const bool own = filter_restricts(filters[perm[g1]]);
-            if (own && n_maps == max_maps) break;
-            qoff.push_back(own ? n_maps : VEC_QMASK_NONE);
-            if (own) { owners.push_back(perm[g1]); n_maps++; }
-            g1++;
-        }
+        // the group: up to GROUP queries, of which at most as many as the bitmap arena holds own a bitmap
+        uint32_t g1, n_maps;
+        VecQMasks qm;
+        if ((rc = build_group_masks(ctx, f, filters, perm.data(), g0, n_scan, GROUP, 0, g1, n_maps, qm))) return rc;
         const uint32_t nq = g1 - g0;
-        VecQMasks qm{nullptr, nullptr, words};
-        if (n_maps) {
-            const uint64_t t0 = timed ? now_us() : 0;
-            VecFilterLists L;
-            if ((rc = upload_filter_lists(ctx, f, filters, owners.data(), n_maps, L))) return rc;
-            const uint64_t t1 = timed ? now_us() : 0;
-            if ((rc = f->d_qbits.reserve((size_t)n_maps * map_bytes)) || (rc = f->d_qoff.reserve((size_t)nq * 4))) return rc;
-            TSGPU_HIP_TRY(hipMemcpyAsync(f->d_qoff.p, qoff.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(vec_qmask_build_kernel, dim3((uint32_t)(((uint64_t)n_maps * words + 255) / 256)), dim3(256), 0, s, L, f->row_ok.as<uint8_t>(), n_rows, words, n_maps,
-                               f->d_qbits.as<uint32_t>());
-            TSGPU_HIP_TRY(hipGetLastError());
-            TSGPU_HIP_TRY(hipStreamSynchronize(s));         // qoff's staging vector dies with this iteration
-            if (timed) { ctx->vec_filter_stage_us += t1 - t0; ctx->vec_filter_build_us += now_us() - t1; }
-            qm.bits = f->d_qbits.as<uint32_t>(); qm.off = f->d_qoff.as<uint32_t>();
-            ctx->vec_filter_scan_queries += n_maps;
-        }
+        ctx->vec_filter_scan_queries += n_maps;
         const VecQMasks* qmp = n_maps ? &qm : nullptr;
         rc = ctx->vec_prefilter
             ? knn_group_prefilter(ctx, f, Qp + (size_t)g0 * f->dim, nq, k, shared_mask, pd + (size_t)g0 * k, pl + (size_t)g0 * k, pc + g0, first, qmp)
@@ -1141,8 +1159,10 @@ int tsgpu_vec_hnsw_export(tsgpu_ctx* ctx, uint32_t vec_field_id, int32_t info[4]
 
 // the traversal kernel over n_q queries (Q_dev, or the rows q_rows[] of the field itself): LDS tier by max(ef, k), visited bookkeeping, the re-runs when a
 // candidate heap or a visited set outgrows its tier. ctx->mu held; results stay on the device. labels = nullptr: internal ids come back.
+// qm: per-query row bitmaps of these n_q queries (tsgpu_vec_hnsw_search_batch_filtered), off[] indexed like Q_dev; null = the one shared mask (the
+// instantiations an unfiltered batch and the bulk build always ran). The re-runs launch the same kind of instantiation with the same maps.
 static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, const uint32_t* q_rows, uint32_t n_q, uint32_t k, uint32_t ef, const uint8_t* mask, bool strict,
-                              const uint64_t* labels, float* d_dist, uint64_t* d_lab, uint32_t* d_cnt, int build_layer = -1) {
+                              const uint64_t* labels, float* d_dist, uint64_t* d_lab, uint32_t* d_cnt, int build_layer = -1, const VecQMasks* qm = nullptr) {
     hipStream_t s = ctx->stream;
     int rc;
     const bool hash_mode = ctx->hnsw_visited_hash != 0;
@@ -1170,6 +1190,7 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
     a.k = k; a.ef = ef; a.ip_lanes = ctx->vec_ip_lanes; a.visited = hash_mode ? nullptr : f->g_visited.as<uint16_t>();
     a.overflow_cnt = f->g_stat.as<uint32_t>();
     a.labels = labels; a.dist_out = d_dist; a.label_out = d_lab; a.n_out = d_cnt;
+    if (qm) { a.qm = *qm; a.qm_n_q = n_q; }              // (n_q, not a.n_q: a re-run overwrites that with its own count, its queries keep their batch index)
     // LDS tier by max(ef, k): result heap 128 / 256 / 512 / 1024 entries, candidate heap 1024 / 1024 / 2048 / 4096 = 13.6 / 14.6 / 25 / 45 KB of LDS per query
     // = 11 / 10 / 6 / 3 queries in flight per CU (the 256 tier — round 6 — is the bulk build's: ef_construction 200 ran on the 512 tier's six before). The
     // queries whose candidate heap (or visited set) outgrows their tier — and only those — run again on the largest (round 6: before, one of them sent the
@@ -1211,11 +1232,18 @@ static int hnsw_search_launch(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, c
             else if (tier == 1) hipLaunchKernelGGL((vec_hnsw_search_kernel<257, 1024, true>), dim3(grid_now), dim3(64), 0, s, a);
             else if (tier == 2) hipLaunchKernelGGL((vec_hnsw_search_kernel<513, 2048, true>), dim3(grid_now), dim3(64), 0, s, a);
             else hipLaunchKernelGGL((vec_hnsw_search_kernel<VEC_HNSW_MAX_EF + 1, VEC_HNSW_CAND_CAP, true>), dim3(grid_now), dim3(64), 0, s, a);
+        } else if (qm) {                                 // per-query row bitmaps
+            if (tier == 0 && tiny) hipLaunchKernelGGL((vec_hnsw_search_kernel<129, 24, false, true>), dim3(grid_now), dim3(64), 0, s, a);
+            else if (tier == 0) hipLaunchKernelGGL((vec_hnsw_search_kernel<129, 1024, false, true>), dim3(grid_now), dim3(64), 0, s, a);
+            else if (tier == 1) hipLaunchKernelGGL((vec_hnsw_search_kernel<257, 1024, false, true>), dim3(grid_now), dim3(64), 0, s, a);
+            else if (tier == 2) hipLaunchKernelGGL((vec_hnsw_search_kernel<513, 2048, false, true>), dim3(grid_now), dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((vec_hnsw_search_kernel<VEC_HNSW_MAX_EF + 1, VEC_HNSW_CAND_CAP, false, true>), dim3(grid_now), dim3(64), 0, s, a);
         } else if (tier == 0 && tiny) hipLaunchKernelGGL((vec_hnsw_search_kernel<129, 24>), dim3(grid_now), dim3(64), 0, s, a);
         else if (tier == 0) hipLaunchKernelGGL((vec_hnsw_search_kernel<129, 1024>), dim3(grid_now), dim3(64), 0, s, a);
         else if (tier == 1) hipLaunchKernelGGL((vec_hnsw_search_kernel<257, 1024>), dim3(grid_now), dim3(64), 0, s, a);
         else if (tier == 2) hipLaunchKernelGGL((vec_hnsw_search_kernel<513, 2048>), dim3(grid_now), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((vec_hnsw_search_kernel<VEC_HNSW_MAX_EF + 1, VEC_HNSW_CAND_CAP>), dim3(grid_now), dim3(64), 0, s, a);
+        ctx->hnsw_launches++;
         uint32_t h_stat[14] = {0};
         TSGPU_HIP_TRY(hipMemcpyAsync(h_stat, a.overflow_cnt, 56, hipMemcpyDeviceToHost, s));
         TSGPU_HIP_TRY(hipStreamSynchronize(s));
@@ -1411,22 +1439,44 @@ int tsgpu_vec_hnsw_build(tsgpu_ctx* ctx, uint32_t vec_field_id, uint32_t M, uint
     return ok();
 }
 
-int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
-                                int functor_present, const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids, uint32_t n_excluded,
-                                float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
-    if (!ctx || !Q || !dist_out || !label_out || !n_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch: NULL argument");
-    if (n_q == 0) return ok();
-    if (k == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch: k must be > 0");
-    if (std::max(k, ef) > VEC_HNSW_MAX_EF) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_hnsw_search_batch: max(k, ef) > 1024 is not accelerated");
-    std::lock_guard<std::mutex> lk(ctx->mu);
+// One traversal per GROUP of consecutive queries, every query with its own filter (tsgpu_vec_hnsw_search_batch_filtered; some query restricts). The
+// restricting queries own row bitmaps, the others keep the shared row_ok test (build_group_masks: the exact path's maps and its 4 GiB arena bound). A
+// batch whose maps do not fit is split, each group one hnsw_search_launch with Q_dev, the outputs and off[] starting at the group. Caller holds ctx->mu.
+static int hnsw_device_filtered(tsgpu_ctx* ctx, VecField* f, const float* Q_dev, uint32_t n_q, uint32_t k, uint32_t ef, bool strict, const tsgpu_vec_filter* filters,
+                                float* d_dist, uint64_t* d_lab, uint32_t* d_cnt) {
+    const uint8_t* shared_mask = f->any_deleted ? f->row_ok.as<uint8_t>() : nullptr;
+    uint64_t tot_exp = 0, tot_dist = 0;
+    int rc;
+    for (uint32_t g0 = 0; g0 < n_q;) {
+        uint32_t g1, n_maps;
+        VecQMasks qm;
+        // (hnsw_test_max_maps, TESTS ONLY: the group split on a few queries)
+        if ((rc = build_group_masks(ctx, f, filters, nullptr, g0, n_q, n_q, ctx->hnsw_test_max_maps, g1, n_maps, qm))) return rc;
+        const uint32_t nq = g1 - g0;
+        ctx->hnsw_filter_maps += n_maps;
+        if ((rc = hnsw_search_launch(ctx, f, Q_dev + (size_t)g0 * f->dim, nullptr, nq, k, ef, shared_mask, strict, f->labels.as<uint64_t>(), d_dist + (size_t)g0 * k,
+                                     d_lab + (size_t)g0 * k, d_cnt + g0, -1, n_maps ? &qm : nullptr))) return rc;
+        tot_exp += ctx->hnsw_last_expansions; tot_dist += ctx->hnsw_last_distances;
+        g0 = g1;
+    }
+    ctx->hnsw_last_expansions = tot_exp; ctx->hnsw_last_distances = tot_dist;      // (the batch's, not its last group's)
+    return TSGPU_OK;
+}
+
+// Both HNSW entry points behind their argument checks; ctx->mu held by the caller. filters != NULL: one filter per query (some query restricts), the
+// single lists are ignored; else the batch's one allow list / excluded list. who: the entry point's name, for the messages.
+static int hnsw_search_locked(tsgpu_ctx* ctx, const char* who, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
+                              int functor_present, const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids, uint32_t n_excluded,
+                              const tsgpu_vec_filter* filters, float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
+    auto bad = [&](int code, const char* msg) { return fail(code, std::string(who) + msg); };
     (void)hipSetDevice(ctx->device);
     VecField* f = get_field(ctx, vec_field_id);
-    if (!f) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_vec_hnsw_search_batch: unknown vector field");
+    if (!f) return bad(TSGPU_ERR_NOT_FOUND, ": unknown vector field");
     if (f->hb) {                                       // the graph is built inside the library: bring the device copy up to date
-        if (f->hb->stale) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_hnsw_search_batch: the built graph no longer matches the rows: use tsgpu_vec_knn_batch");
+        if (f->hb->stale) return bad(TSGPU_ERR_UNSUPPORTED, ": the built graph no longer matches the rows: use tsgpu_vec_knn_batch");
         if (f->hb->dirty || !f->g_loaded || f->g_n != f->n_rows) {
             HnswBuilder& hb = *f->hb;
-            if (hb.size() != f->n_rows) return fail(TSGPU_ERR_DEVICE, "tsgpu_vec_hnsw_search_batch: the builder and the field disagree on the row count");
+            if (hb.size() != f->n_rows) return bad(TSGPU_ERR_DEVICE, ": the builder and the field disagree on the row count");
             std::vector<uint64_t> up(hb.size() + 1);
             for (size_t i = 0; i < hb.size(); i++) up[i] = hb.upper_at[i];
             up[hb.size()] = hb.n_upper_lists();
@@ -1435,14 +1485,14 @@ int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const flo
             hb.dirty = false;
         }
     }
-    if (!f->g_loaded || f->g_n != f->n_rows) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch: no graph loaded for the current rows (tsgpu_vec_hnsw_load / tsgpu_vec_hnsw_enable)");
+    if (!f->g_loaded || f->g_n != f->n_rows) return bad(TSGPU_ERR_INVALID, ": no graph loaded for the current rows (tsgpu_vec_hnsw_load / tsgpu_vec_hnsw_enable)");
     hipStream_t s = ctx->stream;
     try {
         const float* Q_dev = nullptr;
         int rc = stage_queries(ctx, f, Q, mem_q, n_q, &Q_dev);
         if (rc) return rc;
         const uint8_t* mask = nullptr;
-        if ((rc = build_mask(ctx, f, allow_ids, n_allow, excluded_ids, n_excluded, &mask))) return rc;
+        if (!filters && (rc = build_mask(ctx, f, allow_ids, n_allow, excluded_ids, n_excluded, &mask))) return rc;
         float* d_dist = dist_out; uint64_t* d_lab = label_out; uint32_t* d_cnt = n_out;
         if (mem_out != TSGPU_MEM_DEVICE) {
             if ((rc = f->d_dist.reserve((size_t)n_q * k * 4))) return rc;
@@ -1454,7 +1504,10 @@ int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const flo
             TSGPU_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_q * 4, s));
         } else {
             TSGPU_HIP_TRY(hipEventRecord(ctx->ev[3], s));
-            if ((rc = hnsw_search_launch(ctx, f, Q_dev, nullptr, n_q, k, ef, mask, functor_present || f->any_deleted, f->labels.as<uint64_t>(), d_dist, d_lab, d_cnt))) return rc;
+            const bool strict = functor_present || f->any_deleted;
+            if (filters) rc = hnsw_device_filtered(ctx, f, Q_dev, n_q, k, ef, strict, filters, d_dist, d_lab, d_cnt);
+            else rc = hnsw_search_launch(ctx, f, Q_dev, nullptr, n_q, k, ef, mask, strict, f->labels.as<uint64_t>(), d_dist, d_lab, d_cnt);
+            if (rc) return rc;
             TSGPU_HIP_TRY(hipEventRecord(ctx->ev[4], s));
             TSGPU_HIP_TRY(hipEventRecord(ctx->ev[5], s));
             TSGPU_HIP_TRY(hipGetLastError());
@@ -1466,8 +1519,131 @@ int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const flo
         }
         TSGPU_HIP_TRY(hipStreamSynchronize(s));
         if (f->n_rows) { ctx->scan_events_valid = false; knn_collect_timings(ctx); }
-    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_vec_hnsw_search_batch: host allocation failed"); }
+    } catch (const std::bad_alloc&) { return bad(TSGPU_ERR_NO_MEMORY, ": host allocation failed"); }
     return ok();
+}
+
+}  // extern "C"
+
+namespace tsgpu {
+struct HnswRequest : ParkedRequest {
+    uint32_t field = 0, k = 0, ef = 0;
+    int functor = 0;
+    const char* who = "";                            // the entry point the call came through: a round's error reaches every caller under its own
+    const float* Q = nullptr;                        // host, [units][dim]
+    float* dist_out = nullptr; uint64_t* label_out = nullptr; uint32_t* n_out = nullptr;   // host
+    const tsgpu_vec_filter* filters = nullptr;       // [units] the caller's filters, null = none (they stay valid: the caller blocks until its round is done)
+};
+}
+
+// A small HNSW search from one of several concurrent request threads (host/tsgpu_hnsw_adaptor.h issues exactly these: searchKnnCloserFirst = one
+// query, its own filter): the parked calls of one (field, k, ef, functor_present) run as ONE filtered batch — one traversal launch whose wavefronts
+// fill the device instead of one wavefront per call. The rounds are the HNSW path's own (ctx->hnsw_comb: counters "hnsw_batch_rounds" /
+// "hnsw_batch_coalesced_calls"); the exact k-NN rounds and their counters are untouched.
+static int vec_hnsw_coalesced(tsgpu_ctx* ctx, const char* who, uint32_t field, const float* Q, uint32_t n_q, uint32_t k, uint32_t ef, int functor_present, const tsgpu_vec_filter* filters,
+                              float* dist_out, uint64_t* label_out, uint32_t* n_out) {
+    HnswRequest me;
+    me.units = n_q; me.field = field; me.k = k; me.ef = ef; me.functor = functor_present ? 1 : 0; me.Q = Q; me.dist_out = dist_out; me.label_out = label_out; me.n_out = n_out;
+    me.filters = filters; me.who = who;
+    typedef std::unique_lock<std::mutex> Lock;
+    auto acquire = [&]() { return std::unique_ptr<Lock>(new Lock(ctx->mu)); };
+    const uint32_t round_cap = std::max<uint32_t>(ctx->batch_round_queries, n_q);
+    auto pick = [&](std::vector<HnswRequest*>& pending, std::vector<HnswRequest*>& round) {
+        const HnswRequest& r0 = *pending[0];
+        uint32_t units = 0;
+        std::vector<HnswRequest*> rest;
+        for (HnswRequest* r : pending) {
+            if (r->field == r0.field && r->k == r0.k && r->ef == r0.ef && r->functor == r0.functor && (round.empty() || units + r->units <= round_cap)) { round.push_back(r); units += r->units; }
+            else rest.push_back(r);
+        }
+        pending.swap(rest);
+    };
+    auto exec = [&](std::vector<HnswRequest*>& round, std::unique_ptr<Lock>&) {
+        int rc = TSGPU_OK;
+        std::string err;
+        try {
+            VecField* f = get_field(ctx, round[0]->field);
+            if (!f) { rc = TSGPU_ERR_NOT_FOUND; err = ": unknown vector field"; }
+            else {
+                uint32_t total = 0;
+                for (HnswRequest* r : round) total += r->units;
+                const uint32_t kk = round[0]->k;
+                std::vector<float> Qall((size_t)total * f->dim), d((size_t)total * kk);
+                std::vector<uint64_t> l((size_t)total * kk);
+                std::vector<uint32_t> c(total);
+                uint32_t at = 0;
+                for (HnswRequest* r : round) { memcpy(Qall.data() + (size_t)at * f->dim, r->Q, (size_t)r->units * f->dim * 4); at += r->units; }
+                std::vector<tsgpu_vec_filter> fl;                  // every query carries its own lists; a round without a filtered call is the unfiltered batch
+                bool any_filtered = false;
+                for (HnswRequest* r : round) any_filtered = any_filtered || r->filters;
+                if (any_filtered) for (HnswRequest* r : round) {
+                    if (r->filters) fl.insert(fl.end(), r->filters, r->filters + r->units);
+                    else fl.insert(fl.end(), r->units, tsgpu_vec_filter{0, 0, nullptr, 0, nullptr});
+                }
+                rc = hnsw_search_locked(ctx, "", round[0]->field, Qall.data(), TSGPU_MEM_HOST, total, kk, round[0]->ef, round[0]->functor, nullptr, 0, nullptr, 0,
+                                        fl.empty() ? nullptr : fl.data(), d.data(), l.data(), c.data(), TSGPU_MEM_HOST);
+                if (rc != TSGPU_OK) err = tls_error();
+                else {
+                    at = 0;
+                    for (HnswRequest* r : round) {
+                        memcpy(r->dist_out, d.data() + (size_t)at * kk, (size_t)r->units * kk * 4);
+                        memcpy(r->label_out, l.data() + (size_t)at * kk, (size_t)r->units * kk * 8);
+                        memcpy(r->n_out, c.data() + at, (size_t)r->units * 4);
+                        at += r->units;
+                    }
+                }
+            }
+        } catch (const std::bad_alloc&) { rc = TSGPU_ERR_NO_MEMORY; err = ": host allocation failed"; }
+        // (the library's own messages start at the colon: each caller reads them under the entry point IT called; a HIP error's text stays as it is)
+        for (HnswRequest* r : round) { r->rc = rc; r->err = err.compare(0, 2, ": ") == 0 ? r->who + err : err; }
+    };
+    ctx->hnsw_comb.run(me, ctx->hnsw_callers, ctx->batch_window_us, acquire, pick, exec, ctx->vec_batch_post_window_us);
+    if (me.rc != TSGPU_OK) return fail(me.rc, me.err);
+    return ok();
+}
+
+namespace {
+struct HnswCallerCount { std::atomic<int>& c; explicit HnswCallerCount(std::atomic<int>& x) : c(x) { c.fetch_add(1); } ~HnswCallerCount() { c.fetch_sub(1); } };
+// a call the coalescer takes: host in, host out, small, and somebody else is inside either HNSW entry point right now (a lone caller takes the direct path)
+bool hnsw_call_parks(tsgpu_ctx* ctx, int mem_q, int mem_out, uint32_t n_q) {
+    return mem_q == TSGPU_MEM_HOST && mem_out == TSGPU_MEM_HOST && n_q <= ctx->batch_max_queries && ctx->hnsw_callers.load() > 1;
+}
+}
+
+extern "C" {
+
+int tsgpu_vec_hnsw_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef,
+                                int functor_present, const uint32_t* allow_ids, uint32_t n_allow, const uint32_t* excluded_ids, uint32_t n_excluded,
+                                float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
+    if (!ctx || !Q || !dist_out || !label_out || !n_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch: NULL argument");
+    if (n_q == 0) return ok();
+    if (k == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch: k must be > 0");
+    if (std::max(k, ef) > VEC_HNSW_MAX_EF) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_hnsw_search_batch: max(k, ef) > 1024 is not accelerated");
+    HnswCallerCount cc(ctx->hnsw_callers);
+    if (hnsw_call_parks(ctx, mem_q, mem_out, n_q) && (!n_excluded || excluded_ids)) {
+        if (!allow_ids && !n_excluded) return vec_hnsw_coalesced(ctx, "tsgpu_vec_hnsw_search_batch", vec_field_id, Q, n_q, k, ef, functor_present, nullptr, dist_out, label_out, n_out);
+        const std::vector<tsgpu_vec_filter> fl(n_q, tsgpu_vec_filter{allow_ids ? 1u : 0u, allow_ids ? n_allow : 0u, allow_ids, n_excluded, n_excluded ? excluded_ids : nullptr});   // the call's one filter, per query
+        return vec_hnsw_coalesced(ctx, "tsgpu_vec_hnsw_search_batch", vec_field_id, Q, n_q, k, ef, functor_present, fl.data(), dist_out, label_out, n_out);
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return hnsw_search_locked(ctx, "tsgpu_vec_hnsw_search_batch", vec_field_id, Q, mem_q, n_q, k, ef, functor_present, allow_ids, n_allow, excluded_ids, n_excluded, nullptr,
+                              dist_out, label_out, n_out, mem_out);
+}
+
+int tsgpu_vec_hnsw_search_batch_filtered(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, int mem_q, uint32_t n_q, uint32_t k, uint32_t ef, int functor_present,
+                                         const tsgpu_vec_filter* filters, float* dist_out, uint64_t* label_out, uint32_t* n_out, int mem_out) {
+    if (!ctx || !Q || !dist_out || !label_out || !n_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch_filtered: NULL argument");
+    if (n_q == 0) return ok();
+    if (k == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_vec_hnsw_search_batch_filtered: k must be > 0");
+    if (std::max(k, ef) > VEC_HNSW_MAX_EF) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vec_hnsw_search_batch_filtered: max(k, ef) > 1024 is not accelerated");
+    bool any = false;
+    if (int rc = check_filters(filters, n_q, any)) return rc;
+    if (!any) filters = nullptr;                     // no filter restricts: the unfiltered batch, as it is
+    HnswCallerCount cc(ctx->hnsw_callers);
+    if (hnsw_call_parks(ctx, mem_q, mem_out, n_q)) return vec_hnsw_coalesced(ctx, "tsgpu_vec_hnsw_search_batch_filtered", vec_field_id, Q, n_q, k, ef, functor_present, filters, dist_out, label_out, n_out);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return hnsw_search_locked(ctx, "tsgpu_vec_hnsw_search_batch_filtered", vec_field_id, Q, mem_q, n_q, k, ef, functor_present, nullptr, 0, nullptr, 0, filters,
+                              dist_out, label_out, n_out, mem_out);
 }
 
 int tsgpu_vec_distances(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* q, const uint64_t* labels, uint32_t n, float* dist_out) {

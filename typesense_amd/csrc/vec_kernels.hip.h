@@ -60,8 +60,9 @@ __device__ inline float ord_f32(uint32_t o) {
 // The scan kernels take the masks behind a template parameter (PQ): the instantiations an unfiltered batch launches are the code they were.
 // A lane's 16 accumulator rows of one (rb, cb) block are rows g0 + 4 * (lane >> 5) + (el & 3) + 8 * (el >> 2) of the 32-aligned group
 // g0 = r0 + 64 * strip + 32 * rb: ONE word load per (rb, cb) and lane decides all of them.
-// Out of scope here: per-query masks in vec_hnsw_search_kernel, a per-query parameter block for tsgpu_vector_search_batch, the
-// tsgpu_group_* shard forms (they keep their per-query loop), filters that already live on the device.
+// vec_hnsw_search_kernel's PQ instantiations (tsgpu_vec_hnsw_search_batch_filtered) read the same maps, one bit per admission test.
+// Out of scope here: a per-query parameter block for tsgpu_vector_search_batch, the tsgpu_group_* shard forms (they keep their
+// per-query loop), filters that already live on the device.
 static const uint32_t VEC_QMASK_NONE = 0xFFFFFFFFu;
 struct VecQMasks {
     const uint32_t* bits;      // [n_maps][words]
@@ -1430,6 +1431,8 @@ struct VecHnswArgs {
     uint32_t* overflow_cnt;                             // [0] queries whose candidate heap outgrew CANDCAP; [1] queries whose visited set passed half full; [2..3] u64 expansions, [4..5] u64 distances (batch totals)
     const uint64_t* labels;                             // nullable: internal ids come back
     float* dist_out; uint64_t* label_out; uint32_t* n_out;   // [n_q][k]; n_out = 0xFFFFFFFF: candidate heap overflow (caller re-runs exactly)
+    VecQMasks qm;              // PQ instantiations only: per-query row bitmaps, off[] indexed by the BATCH index of a query (q_sel[qn] on a re-run) ...
+    uint32_t qm_n_q;           // ... and bounds-checked against the batch's own query count (n_q is the re-run's count on a re-run)
 };
 static const uint32_t VEC_HNSW_SET_FULL = 0xFFFFFFFEu;   // n_out between the launches of one search only: never handed to the caller
 #ifndef TSGPU_HNSW_ROWS
@@ -1488,9 +1491,19 @@ struct HnswHeap {          // max-heap on .d (CompareByFirst: a.first < b.first)
     }
 };
 
+// May row `id` enter the result heap? hnswlib asks `!isMarkedDeleted(id) && (!filter || (*filter)(label))`; here that is ONE BIT of the query's own
+// map (PQ, qbits = vec_qmask_of: deleted rows, its allow list and its excluded ids are folded in), or the byte of the mask the whole batch shares
+// (qbits == nullptr: the query has no filter of its own; always so without PQ). The only two admission sites of the traversal call this.
+template <bool PQ>
+__device__ inline bool vec_hnsw_admits(const VecHnswArgs& a, const uint32_t* __restrict__ qbits, uint32_t id) {
+    if (PQ && qbits) return ((qbits[id >> 5] >> (id & 31)) & 1u) != 0;
+    return !a.row_ok || a.row_ok[id] != 0;
+}
+
 // TOPCAP >= max(ef, k) + 1, CANDCAP = candidate heap capacity: LDS tiers chosen by the host from ef, so that a CU holds as many
 // concurrent queries as its wave slots allow at the usual ef (13 KB per query at ef <= 128 instead of 45 KB).
-template <uint32_t TOPCAP, uint32_t CANDCAP, bool BUILD = false>
+// PQ = the queries bring their own row bitmaps (a.qm): the upper layers stay unfiltered, as in hnswlib; nothing but the admission test differs.
+template <uint32_t TOPCAP, uint32_t CANDCAP, bool BUILD = false, bool PQ = false>
 __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
     const uint32_t base = BUILD ? a.base_level : 0u;
     __shared__ HnswEntry top_e[TOPCAP];
@@ -1521,6 +1534,7 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
     for (uint32_t qn = blockIdx.x; qn < a.n_q; qn += gridDim.x, iter++) {
         const uint32_t q = a.q_sel ? a.q_sel[qn] : qn;
         const uint16_t epoch = (uint16_t)(a.epoch_base + iter);
+        const uint32_t* __restrict__ qbits = PQ ? vec_qmask_of(a.qm, q, a.qm_n_q) : nullptr;      // THIS query's map (per query: re-derived here, not kept across queries)
         uint32_t n_vis = 0;                                      // (per lane; summed over the wave when checked)
         if (vset) {
             for (uint32_t i = lane; i < a.vhash_slots; i += 64) vset[i] = 0u;
@@ -1589,7 +1603,7 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
 #define HNSW_PROF(i)
 #endif
         if (lane == 0) {
-            const bool ok = !a.row_ok || a.row_ok[cur] != 0;
+            const bool ok = vec_hnsw_admits<PQ>(a, qbits, cur);
             if (ok) { lowerBound = curdist; top.push(curdist, cur); cand.push(-curdist, cur); }
             else { lowerBound = 3.402823466e+38f; cand.push(-lowerBound, cur); }
             (void)visit(cur, epoch, n_vis);
@@ -1626,7 +1640,7 @@ __global__ __launch_bounds__(64) void vec_hnsw_search_kernel(VecHnswArgs a) {
             if (fresh) {
                 const uint32_t slot = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));      // unvisited neighbours, list order kept
                 nb_id[slot] = c;
-                nb_ok[slot] = (!a.row_ok || a.row_ok[c] != 0) ? 1 : 0;
+                nb_ok[slot] = vec_hnsw_admits<PQ>(a, qbits, c) ? 1 : 0;
             }
             __syncthreads();
             HNSW_PROF(1)

@@ -540,14 +540,9 @@ class GpuIndex:
                                             _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
         return dist, lab, cnt
 
-    def vec_knn_batch_filtered(self, field_id, Q, k, filters):
-        """tsgpu_vec_knn_batch_filtered: one exact k-NN batch in which query i has its own filter. filters: None (no query is filtered) or one entry
-        per query: None (no filter) or (allow_ids | None, excluded_ids | None); sorted seq_ids; an EMPTY allow list allows nothing"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
-        n = Q.shape[0]
-        dist = np.zeros((n, k), np.float32)
-        lab = np.zeros((n, k), np.uint64)
-        cnt = np.zeros(n, np.uint32)
+    @staticmethod
+    def _vec_filters(filters, n):
+        """-> (tsgpu_vec_filter[n] | None, the arrays it points into)"""
         arr, keep = None, []
         if filters is not None:
             assert len(filters) == n
@@ -564,6 +559,17 @@ class GpuIndex:
                     e = _u32(excl)
                     keep.append(e)
                     arr[i].n_excluded, arr[i].excluded_ids = e.size, e.ctypes.data if e.size else None
+        return arr, keep
+
+    def vec_knn_batch_filtered(self, field_id, Q, k, filters):
+        """tsgpu_vec_knn_batch_filtered: one exact k-NN batch in which query i has its own filter. filters: None (no query is filtered) or one entry
+        per query: None (no filter) or (allow_ids | None, excluded_ids | None); sorted seq_ids; an EMPTY allow list allows nothing"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
+        n = Q.shape[0]
+        dist = np.zeros((n, k), np.float32)
+        lab = np.zeros((n, k), np.uint64)
+        cnt = np.zeros(n, np.uint32)
+        arr, keep = self._vec_filters(filters, n)
         self._ck(self.L.tsgpu_vec_knn_batch_filtered(self.h, field_id, _vp(Q), B.MEM_HOST, n, k, arr, _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
         return dist, lab, cnt
 
@@ -610,6 +616,16 @@ class GpuIndex:
                                                     _vp(a) if a is not None else None, a.size if a is not None else 0,
                                                     _vp(e) if e is not None else None, e.size if e is not None else 0,
                                                     _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
+        return dist, lab, cnt
+
+    def vec_hnsw_search_batch_filtered(self, field_id, Q, k, ef, filters, functor_present=True):
+        """tsgpu_vec_hnsw_search_batch_filtered: one HNSW batch in which query i has its own filter; filters as vec_knn_batch_filtered takes them"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
+        n = Q.shape[0]
+        dist = np.zeros((n, k), np.float32); lab = np.zeros((n, k), np.uint64); cnt = np.zeros(n, np.uint32)
+        arr, keep = self._vec_filters(filters, n)
+        self._ck(self.L.tsgpu_vec_hnsw_search_batch_filtered(self.h, field_id, _vp(Q), B.MEM_HOST, n, k, ef, int(functor_present), arr,
+                                                             _vp(dist), _vp(lab), _vp(cnt), B.MEM_HOST))
         return dist, lab, cnt
 
     def vec_hnsw_search_batch_raw(self, field_id, q_ptr, mem_q, n, k, ef, dist_ptr, lab_ptr, cnt_ptr, mem_out, functor_present=True):
