@@ -89,7 +89,7 @@ enum tsgpu_sort_kind {
      * wildcard, candidates and grouped entry points of ONE context. tsgpu_vector_search_batch, tsgpu_hybrid_* (there the reference walks the hits in
      * distance order with the forward-only cursor of :5817: not membership) and every tsgpu_group_* shard form answer 501 for a query that names one.
      * Out of scope, 501 / left to the caller's CPU body: geo-distance sort (needs S2), the decay functions (libm's exp bit for bit), random_order,
-     * _vector_query(...) sort, reference / join sorts, _group_found; text-match and vector-distance bucketing happen after the Topster, on the host. */
+     * reference / join sorts, _group_found; text-match and vector-distance bucketing happen after the Topster, on the host. */
     TSGPU_SORT_EVAL = 4,            /* _eval(<filters>): `column` holds a sort-key HANDLE (tsgpu_sort_key_create_eval); the score is scores[e] of the FIRST
                                        expression e whose id list holds the document, else 0 (:5809-5834). At most one _eval slot per query (501 beyond:
                                        the reference shares one cursor vector between them, :5809-5811, its result depends on their order) */
@@ -98,8 +98,14 @@ enum tsgpu_sort_kind {
                                        missing_values: normal ARE kind 2 as it stands (INT64_MIN sorts last either way: -INT64_MIN == INT64_MIN) */
     TSGPU_SORT_STRING_RANK = 6,     /* sort on a string field: `column` is an int64 column of adi_tree_t::rank(seq_id) values, INT64_MAX (adi_tree_t::NOT_FOUND)
                                        for a document without a value (:5733-5735); then as kind 2 */
-    TSGPU_SORT_STRING_RANK_FLIP = 7 /* kind 6, but a value equal to INT64_MAX is negated first (:5750-5760, wrapping). The caller picks 7 exactly when
+    TSGPU_SORT_STRING_RANK_FLIP = 7,/* kind 6, but a value equal to INT64_MAX is negated first (:5750-5760, wrapping). The caller picks 7 exactly when
                                        (order asc AND missing_values first) OR (order desc AND missing_values last) */
+    /* 8 is NOT a kind: it stays unassigned and answers 501 like every value beyond 9 */
+    TSGPU_SORT_VECTOR_QUERY = 9     /* _vector_query(<field>:([...])), :5837-5851: `column` holds a sort-key HANDLE (tsgpu_sort_key_create_vector_query); the score is
+                                       float_to_int64_t(d), d = the exact distance of the key's query to the document's row of the key's vector field — the raw
+                                       dist_func value (no abs() for cosine), summed in the order option "vec_ip_lanes" selects when the batch runs; d > the key's
+                                       distance_threshold -> FLT_MAX (equal stays); a document without a live row scores float_to_int64_t(2.0f). Up to three such
+                                       slots per query, next to at most one _eval slot. Evaluated inside the keyword kernels, one distance per emitted hit */
 };
 #define TSGPU_SORT_KEY_SLOTS 4096   /* sort-key handles that can be live at once per context (256 request threads x 3 slots, with room to spare) */
 
@@ -247,6 +253,14 @@ int tsgpu_set_num_docs(tsgpu_ctx* ctx, uint32_t num_docs);
  * Counter "sort_keys_live". */
 int tsgpu_sort_key_create_eval(tsgpu_ctx* ctx, const uint32_t* const* ids, const uint32_t* n_ids, const int64_t* scores, uint32_t n_expr, uint16_t* handle_out);
 int tsgpu_sort_key_destroy(tsgpu_ctx* ctx, uint16_t handle);
+/* The key a TSGPU_SORT_VECTOR_QUERY slot carries: q = vector_query.query.values (host, the field's dim floats; for a cosine field the library normalises its
+ * copy like hnsw_index_t::normalize_vector, src/collection.cpp:1445-1448), distance_threshold = vector_query.query.distance_threshold (FLT_MAX = none).
+ * A handle of the same table as the _eval keys (TSGPU_SORT_KEY_SLOTS, counter "sort_keys_live"), freed with tsgpu_sort_key_destroy. The key NAMES its
+ * field: a search reads the field's rows as they are when its batch runs (upserts, updates and deletes since the key was created count). A batch that names
+ * such a key holds the context's index lock while it runs, so vector mutations wait for it and it for them; batches without one take no lock.
+ * 400: NULL argument; 404: unknown vector field; 507: every handle is live. A TSGPU_SORT_EVAL slot naming such a key, or a TSGPU_SORT_VECTOR_QUERY slot
+ * naming an _eval key or a handle that is not live, gets 400. */
+int tsgpu_sort_key_create_vector_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* q, float distance_threshold, uint16_t* handle_out);
 
 /* Publish all pending posting-list changes as ONE new immutable snapshot (RCU): searches that started before keep the snapshot they
  * run on, searches never wait for a commit, a failing commit leaves the previous snapshot in place. Incremental: re-written blocks
@@ -278,7 +292,7 @@ int tsgpu_term_blocks_download(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_
 typedef struct tsgpu_sort_by {
     uint8_t kind;      /* tsgpu_sort_kind */
     int8_t order;      /* 1 = DESC, -1 = ASC (sort_order[], src/index.cpp:5901-5903) */
-    uint16_t column;   /* column id (kinds 2, 5, 6, 7) or sort-key handle (TSGPU_SORT_EVAL) */
+    uint16_t column;   /* column id (kinds 2, 5, 6, 7) or sort-key handle (TSGPU_SORT_EVAL, TSGPU_SORT_VECTOR_QUERY) */
 } tsgpu_sort_by;
 
 typedef struct tsgpu_kw_query {

@@ -9,6 +9,7 @@ TSGPU_OK, ERR_INVALID, ERR_NOT_FOUND, ERR_DEADLINE, ERR_DEVICE, ERR_UNSUPPORTED,
 MEM_HOST, MEM_DEVICE = 0, 1
 SORT_TEXT_MATCH, SORT_SEQ_ID, SORT_INT64_COLUMN, SORT_VECTOR_DISTANCE = 0, 1, 2, 3
 SORT_EVAL, SORT_INT64_COLUMN_MISSING_FIRST, SORT_STRING_RANK, SORT_STRING_RANK_FLIP = 4, 5, 6, 7
+SORT_VECTOR_QUERY = 9       # (8 is no kind)
 SORT_KEY_SLOTS = 4096
 METRIC_IP, METRIC_COSINE = 0, 1
 MAX_SCORE, MAX_WEIGHT, SUM_SCORE = 0, 1, 2
@@ -131,7 +132,7 @@ class HostCollectivesC(C.Structure):
 
 EXPORTS = [
     "tsgpu_abi_version", "tsgpu_create", "tsgpu_destroy", "tsgpu_last_error", "tsgpu_set_stream", "tsgpu_set_option", "tsgpu_get_counter", "tsgpu_device_bytes",
-    "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_destroy", "tsgpu_commit",
+    "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_create_vector_query", "tsgpu_sort_key_destroy", "tsgpu_commit",
     "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_term_blocks_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
     "tsgpu_keyword_search_batch_ids", "tsgpu_keyword_search_grouped_batch", "tsgpu_keyword_search_grouped_candidates_batch", "tsgpu_id_lists_count", "tsgpu_id_lists_ids", "tsgpu_id_lists_free", "tsgpu_facet_set", "tsgpu_facet_count_batch", "tsgpu_facet_count_grouped_batch", "tsgpu_facet_range_count_batch", "tsgpu_facet_stats_batch", "tsgpu_facet_value_set", "tsgpu_facet_value_count_batch",
     "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch", "tsgpu_vec_knn_batch_filtered",
@@ -181,6 +182,7 @@ def lib(path=None):
     L.tsgpu_column_set.argtypes = [vp, u32, vp, vp, u32, i32]
     L.tsgpu_set_num_docs.argtypes = [vp, u32]
     L.tsgpu_sort_key_create_eval.argtypes = [vp, vp, vp, vp, u32, C.POINTER(C.c_uint16)]
+    L.tsgpu_sort_key_create_vector_query.argtypes = [vp, u32, vp, C.c_float, C.POINTER(C.c_uint16)]
     L.tsgpu_sort_key_destroy.argtypes = [vp, C.c_uint16]
     L.tsgpu_commit.argtypes = [vp]
     L.tsgpu_term_num_ids.argtypes = [vp, u32, u32]

@@ -133,18 +133,21 @@ __global__ __launch_bounds__(GB_THREADS) void gb_iota_kernel(GbArgs a) {
 }
 
 // ---- scoring of every matched id ----
-template <int TMAX>                                                          // 3: every query of the batch has <= 3 lists (a fifth of the registers of the 10-token form)
+template <int TMAX, bool VQ = false>                                         // 3: every query of the batch has <= 3 lists (a fifth of the registers of the 10-token form)
 __global__ __launch_bounds__(TMAX <= 3 ? GB_THREADS : 64) void gb_score_kernel(IndexView ix, GbArgs a) {      // (the 10-token form holds 40 positions per thread: one wave per workgroup)
     uint32_t qi; uint64_t i;
-    if (!gb_item_of<(TMAX <= 3 ? GB_THREADS : 64)>(a, qi, i)) return;
+    const bool live = gb_item_of<(TMAX <= 3 ? GB_THREADS : 64)>(a, qi, i);
+    if constexpr (!VQ) { if (!live) return; }                                // VQ (some combination has a TSGPU_SORT_VECTOR_QUERY slot): nobody leaves, the whole wave fills the slot in
     const GbQuery g = a.gq[qi];
     uint32_t c = g.first_combo;                                              // the combination that met this id (<= 16 per user query)
-    while (c + 1 < g.first_combo + g.n_combos && a.combo_begin[c + 1] <= i) c++;
-    a.pass[i] = (uint8_t)(c - g.first_combo);
+    if (live) while (c + 1 < g.first_combo + g.n_combos && a.combo_begin[c + 1] <= i) c++;
+    if (live) a.pass[i] = (uint8_t)(c - g.first_combo);
     const KwQueryDev& q = a.queries[c];
-    const uint32_t seq_id = a.ids[i];
+    const uint32_t seq_id = live ? a.ids[i] : 0u;
     ScoredHit h;
-    if (g.wildcard) {
+    h.s0 = h.s1 = h.s2 = h.text_match = 0; h.off_words = 0;
+    if (!live) {
+    } else if (g.wildcard) {
         h = sort_scores(ix, q, seq_id, 100, 0, false, 0.0f);                 // Index::search_wildcard: the text-match slot is the constant 100 (src/index.cpp:6728-6730)
     } else {
         const KwQueryMF& mf = a.mfs[c];
@@ -168,6 +171,8 @@ __global__ __launch_bounds__(TMAX <= 3 ? GB_THREADS : 64) void gb_score_kernel(I
         const uint64_t agg = agg_score_mf<TMAX>(ix, q, mf, pos, tokens_found, off_words);
         h = sort_scores(ix, q, seq_id, agg, off_words);
     }
+    if constexpr (VQ) wave_vq_sort_patch(ix, q, seq_id, live, h);
+    if (!live) return;
     a.s0[i] = h.s0; a.s1[i] = h.s1; a.s2[i] = h.s2;
     const uint32_t col = g.column;
     // the group column holds get_distinct_id's result per seq_id; a document beyond it has no value in any group_by field (src/index.cpp:7104-7111)

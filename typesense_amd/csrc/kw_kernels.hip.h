@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "tsgpu_format.h"
+#include "vec_ip_order.hip.h"      // the `_vector_query` sort slot (kw_vq_sort.hip.h) takes its distances in the k-NN paths' summation orders
 
 #include <type_traits>
 
@@ -111,6 +112,10 @@ static const int KW_TILE_WORDS = TSGPU_KW_TILE_WORDS;   // LDS tile of PACKED se
 // One `_eval(...)` sort key (tsgpu_sort_key_create_eval; compute_sort_scores, src/index.cpp:5761-5834): the id lists of its expressions in one of two forms.
 // DENSE: dense[seq_id] = first matching expression + 1, 0 = none (one byte load per candidate). SPARSE (dense == nullptr): the sorted lists back to back in
 // ids[], expression e = ids[expr_off[e] .. expr_off[e + 1]), probed by binary search, expression by expression. scores[e] either way.
+// The same table holds the `_vector_query(...)` keys (tsgpu_sort_key_create_vector_query, form = SORT_KEY_FORM_VECTOR_QUERY; :5837-5851, kw_vq_sort.hip.h):
+// the stored query and the key's vector field AS IT IS WHEN THE BATCH RUNS — a batch that names such a key rewrites the vq_ fields behind `vq_q` under
+// ctx->mu before its kernels start (the row matrix may have moved, the row map been rebuilt) and holds the mutex until they have finished.
+static const uint32_t SORT_KEY_FORM_EVAL = 0, SORT_KEY_FORM_VECTOR_QUERY = 1;
 struct SortKeyDesc {
     const uint8_t* dense;
     const uint32_t* ids;
@@ -118,6 +123,16 @@ struct SortKeyDesc {
     const int64_t* scores;           // [n_expr]
     uint32_t dense_len;              // bytes of dense[] (seq_ids beyond it match nothing)
     uint32_t n_expr;
+    uint32_t form;                   // SORT_KEY_FORM_*; the fields above belong to the _eval form, the fields below to the vector-query form
+    uint32_t vq_dim;
+    const float* vq_q;               // [vq_dim] the query, normalised at creation for a cosine field (16-byte aligned)
+    const float* vq_X;               // the field's rows [vq_n_rows][vq_dim]
+    const uint32_t* vq_row_of_seq;   // [vq_map_len] seq_id -> row, 0xFFFFFFFF = none; nullptr: identity numbering (row = seq_id)
+    const uint8_t* vq_row_ok;        // [vq_n_rows] 0 = deleted
+    uint32_t vq_n_rows;
+    uint32_t vq_map_len;
+    float vq_threshold;              // distance_threshold (FLT_MAX = none)
+    uint32_t vq_ip_lanes;            // option vec_ip_lanes when the batch started
 };
 static const uint32_t KW_SORT_KEY_SLOTS = 4096;     // handles of the context's key table (IndexView::sort_keys)
 
@@ -1036,6 +1051,7 @@ __global__ __launch_bounds__(256) void sort_key_scatter_kernel(const uint32_t* _
 // the sort kinds beyond the four of the headline path (include/tsgpu.h): _eval, missing_values: first on a numeric column, string ranks
 __device__ inline int64_t sort_key_value(const IndexView& ix, uint32_t kind, uint32_t col, int order, uint32_t seq_id) {
     if (kind == 4) return sort_key_eval(ix.sort_keys[col < KW_SORT_KEY_SLOTS ? col : 0], seq_id);
+    if (kind == 9) return 0;                   // TSGPU_SORT_VECTOR_QUERY: the wave fills the slot in afterwards (wave_vq_sort_patch, kw_vq_sort.hip.h)
     int64_t v = (col < ix.n_columns && seq_id < ix.column_len[col]) ? ix.columns[col][seq_id] : (kind == 5 ? INT64_MIN : INT64_MAX);
     if (kind == 5) { if (v == INT64_MIN) v = order == -1 ? INT64_MIN + 1 : INT64_MAX; }                 // (:5892-5898)
     else if (kind == 7 && v == INT64_MAX) v = (int64_t)(0ull - (uint64_t)v);                            // adi_tree_t::NOT_FOUND, flipped (:5750-5760)
@@ -1074,6 +1090,8 @@ __device__ inline ScoredHit sort_scores(const IndexView& ix, const KwQueryDev& q
     h.off_words = off_words;
     return h;
 }
+
+#include "kw_vq_sort.hip.h"
 
 
 // score_results2 + compute_aggregated_score + compute_sort_scores for ONE query_by field (plain string); pos[t] = posting
@@ -1296,7 +1314,8 @@ struct KwSmem {
 
 // PLAIN (score kernel only): no query of the launch has filter ids, excluded ids or a sort slot of kind >= TSGPU_SORT_EVAL and no caller keeps the matched ids — the host knows, and the
 // instantiation without those paths is a smaller kernel (registers, not LDS, set the score kernel's occupancy).
-template <int TMAX, int CAP, bool MF, bool S2, bool SCORE, bool PLAIN = false>
+// VQ: some query of the launch has a TSGPU_SORT_VECTOR_QUERY slot (the host knows): only those launches carry the wave-cooperative distance code (kw_vq_sort.hip.h).
+template <int TMAX, int CAP, bool MF, bool S2, bool SCORE, bool PLAIN = false, bool VQ = false>
 __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& sm, const IndexView& ix, const KwQueryDev& q, uint32_t n_take,
                                       const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out, uint32_t ids_out_base) {
     // make room: at most n_take (<=256) new entries. (The score kernel decides AFTER scoring, from the number of hits that beat the
@@ -1341,6 +1360,7 @@ __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& s
             }
         }
     }
+    if constexpr (VQ) wave_vq_sort_patch(ix, q, seq_id, emit, h);          // (every lane of the wave is here; hits that are not emitted cost no distance)
     // num_keyword_matches under a filter (kw_filter_count below): which intersection ids does the reference's loop VISIT?
     if constexpr (PLAIN) {
     } else if (MF && q.n_filt) {
@@ -1547,7 +1567,7 @@ __device__ inline void kw_write_partial(KwSmem<TMAX, CAP, MF, S2, false, SCORE>&
 // to hits[hit_off[work item] ..] as KwHitRec, part.cnt[work item] = how many; kw_score_kernel scores them with full wavefronts.
 // Splitting takes the scoring code's registers and the top-K buffer's LDS out of the merge loop (more resident waves there) and
 // lets the score stage run on dense batches instead of on whatever a work item's queue holds when it flushes.
-template <int TMAX, int CAP, bool S2, bool DEFER = false>
+template <int TMAX, int CAP, bool S2, bool DEFER = false, bool VQ = false>
 __global__ __launch_bounds__(KW_THREADS) KW_FOUR_WAVES_PER_SIMD void kw_search_kernel(IndexView ix, const KwQueryDev* __restrict__ queries,
                                                                 const KwWorkItem* __restrict__ work, KwPartials part,
                                                                 const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out,
@@ -1826,7 +1846,7 @@ __global__ __launch_bounds__(KW_THREADS) KW_FOUR_WAVES_PER_SIMD void kw_search_k
                 while (sm.q1_cnt >= KW_THREADS) {
                     kw_probe_rest_stage<TMAX, CAP, S2, DEFER>(sm, ix, q, KW_THREADS, hits);
                     if constexpr (!DEFER)
-                        while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
+                        while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false, false, VQ>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
                 }
                 q1n = sm.q1_cnt;
             }
@@ -1855,7 +1875,7 @@ __global__ __launch_bounds__(KW_THREADS) KW_FOUR_WAVES_PER_SIMD void kw_search_k
                 __syncthreads();
                 if (t == 0) sm.qf_cnt = qfn;
                 __syncthreads();
-                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
+                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false, false, VQ>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
                 qfn = sm.qf_cnt;
             }
         }
@@ -1870,13 +1890,13 @@ __global__ __launch_bounds__(KW_THREADS) KW_FOUR_WAVES_PER_SIMD void kw_search_k
         while (sm.q1_cnt > 0) {
             kw_probe_rest_stage<TMAX, CAP, S2, DEFER>(sm, ix, q, sm.q1_cnt < KW_THREADS ? sm.q1_cnt : KW_THREADS, hits);
             if constexpr (!DEFER)
-                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
+                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, false, S2, false, false, VQ>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, ids_out_base);
         }
     }
     if constexpr (DEFER) {
         if (t == 0) part.cnt[blockIdx.x] = sm.qf_cnt;              // hits handed to kw_score_kernel
     } else {
-        while (sm.qf_cnt > 0) kw_score_stage<TMAX, CAP, false, S2, false>(sm, ix, q, sm.qf_cnt < KW_THREADS ? sm.qf_cnt : KW_THREADS, aux_ids, my_ids_out, ids_out_base);
+        while (sm.qf_cnt > 0) kw_score_stage<TMAX, CAP, false, S2, false, false, VQ>(sm, ix, q, sm.qf_cnt < KW_THREADS ? sm.qf_cnt : KW_THREADS, aux_ids, my_ids_out, ids_out_base);
         KW_PROF(8)
         // ---- partial result of this work item: sorted, <= k entries ----
         kw_write_partial(sm, q, part, blockIdx.x);
@@ -1890,7 +1910,7 @@ __global__ __launch_bounds__(KW_THREADS) KW_FOUR_WAVES_PER_SIMD void kw_search_k
 // top-K buffer and filter bookkeeping as the fused kernel, and leave the same partial result for kw_merge_kernel.
 // (body = a device function with the work item's index as a parameter; round 5's one-launch round kernel, measured slower and removed in round 6 —
 //  profiles/r05/exp_one_launch_rounds.txt — ran it behind the find body)
-template <int TMAX, int CAP, bool S2, bool MF = false, bool PLAIN = false>
+template <int TMAX, int CAP, bool S2, bool MF = false, bool PLAIN = false, bool VQ = false>
 __device__ __forceinline__ void kw_score_body(const IndexView& ix, const KwQueryDev* __restrict__ queries, const KwWorkItem* __restrict__ work,
                                               const KwPartials& part, const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out,
                                               const uint32_t* __restrict__ hits_all, const uint64_t* __restrict__ hit_off, const uint32_t bid) {
@@ -1929,15 +1949,15 @@ __device__ __forceinline__ void kw_score_body(const IndexView& ix, const KwQuery
         }
         if (t == 0) sm.qf_cnt = n;
         __syncthreads();
-        kw_score_stage<TMAX, CAP, MF, S2, true, PLAIN>(sm, ix, q, n, aux_ids, my_ids_out, 0u);
+        kw_score_stage<TMAX, CAP, MF, S2, true, PLAIN, VQ>(sm, ix, q, n, aux_ids, my_ids_out, 0u);
     }
     kw_write_partial(sm, q, part, bid);
 }
-template <int TMAX, int CAP, bool S2, bool MF = false, bool PLAIN = false>
+template <int TMAX, int CAP, bool S2, bool MF = false, bool PLAIN = false, bool VQ = false>
 __global__ __launch_bounds__(KW_THREADS) KW_SCORE_WAVES void kw_score_kernel(IndexView ix, const KwQueryDev* __restrict__ queries, const KwWorkItem* __restrict__ work,
                                                               KwPartials part, const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out,
                                                               const uint32_t* __restrict__ hits_all, const uint64_t* __restrict__ hit_off) {
-    kw_score_body<TMAX, CAP, S2, MF, PLAIN>(ix, queries, work, part, aux_ids, ids_out, hits_all, hit_off, blockIdx.x);
+    kw_score_body<TMAX, CAP, S2, MF, PLAIN, VQ>(ix, queries, work, part, aux_ids, ids_out, hits_all, hit_off, blockIdx.x);
 }
 
 // LDS-DMA tile fill: N slabs of 256 words, lane t of the workgroup copies word (slab * 256 + t) of the run straight from global memory
@@ -2098,7 +2118,7 @@ __device__ inline void kw_mf_merge_field(SM& sm, const IndexView& ix, const List
 // satisfied by any field, include/or_iterator.h + src/or_iterator.cpp:95-171); complete hits carry their position in every
 // (token, field) list into the shared score stage. Per-candidate probes, no block merge: the slow, general path.
 // DEFER = true: the find half of the two-kernel form (records of 1 + TMAX x KW_MAX_FIELDS words -> kw_score_kernel<.., MF = true>)
-template <int TMAX, int CAP, bool DEFER = false>
+template <int TMAX, int CAP, bool DEFER = false, bool VQ = false>
 __global__ __launch_bounds__(KW_THREADS) void kw_search_mf_kernel(IndexView ix, const KwQueryDev* __restrict__ queries,
                                                                    const KwWorkItem* __restrict__ work, KwPartials part,
                                                                    const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out,
@@ -2212,7 +2232,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_search_mf_kernel(IndexView ix, 
                 __syncthreads();
                 if (t == 0) sm.qf_cnt = qfn;
                 __syncthreads();
-                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, true, true, false>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, 0u);
+                while (sm.qf_cnt >= KW_THREADS) kw_score_stage<TMAX, CAP, true, true, false, false, VQ>(sm, ix, q, KW_THREADS, aux_ids, my_ids_out, 0u);
                 qfn = sm.qf_cnt;
             }
         }
@@ -2307,7 +2327,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_search_mf_kernel(IndexView ix, 
     __syncthreads();
     if (t == 0) sm.qf_cnt = qfn;
     __syncthreads();
-    while (sm.qf_cnt > 0) kw_score_stage<TMAX, CAP, true, true, false>(sm, ix, q, sm.qf_cnt < KW_THREADS ? sm.qf_cnt : KW_THREADS, aux_ids, my_ids_out, 0u);
+    while (sm.qf_cnt > 0) kw_score_stage<TMAX, CAP, true, true, false, false, VQ>(sm, ix, q, sm.qf_cnt < KW_THREADS ? sm.qf_cnt : KW_THREADS, aux_ids, my_ids_out, 0u);
     topk_compact<CAP, decltype(sm)::HAS_S2>(sm.tk, &sm.tk_cnt, q.k, sm.thr, &sm.have_thr);
     const uint32_t n = sm.tk_cnt;
     const size_t base = (size_t)blockIdx.x * part.k_stride;
@@ -2329,7 +2349,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_search_mf_kernel(IndexView ix, 
 // (compute_sort_scores(..., 100, ...), :6728-6730, sign-flipped for ASC, no :5541 override) — into a Topster. The reference
 // splits the id array over threads and merges per-thread Topsters; here a work item = 256-id blocks [blk_begin, blk_end) of the
 // id array, partial top-K per work item, kw_merge_kernel folds them. A pure column gather: one 8-byte load per id and key.
-template <int CAP>
+template <int CAP, bool VQ = false>            // VQ: some query of the launch has a TSGPU_SORT_VECTOR_QUERY slot (kw_vq_sort.hip.h)
 __global__ __launch_bounds__(KW_THREADS) void kw_wildcard_kernel(IndexView ix, const KwQueryDev* __restrict__ queries,
                                                                   const KwWorkItem* __restrict__ work, KwPartials part,
                                                                   const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out) {
@@ -2373,6 +2393,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_wildcard_kernel(IndexView ix, c
             }
             if (emit) h = sort_scores(ix, q, seq_id, q.vdist ? 0 : 100, 0, false, vd);      // (text-match slot: 100 for q=*, 0 in the vector branch :3711)
         }
+        if constexpr (VQ) wave_vq_sort_patch(ix, q, seq_id, emit, h);
         uint32_t total;
         const uint32_t my = block_compact(emit, wave_cnt, total);
         if (emit && my_ids_out) my_ids_out[s_emit + my] = seq_id;

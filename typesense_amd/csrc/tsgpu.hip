@@ -81,21 +81,24 @@ IndexView make_view(tsgpu_ctx* ctx, const Snapshot& sn) {
 
 template <int TMAX, int CAP>
 void launch_search(hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w,
-                   const KwPartials& part, const uint32_t* aux, uint32_t* ids_out, bool s2) {
+                   const KwPartials& part, const uint32_t* aux, uint32_t* ids_out, bool s2, bool vq = false) {
     // s2 = some query of the launch sorts by three keys; the two-key build (CAP 512 only) has a smaller LDS footprint
-    if (CAP == 512 && !s2) hipLaunchKernelGGL((kw_search_kernel<TMAX, CAP, CAP != 512>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
+    // vq = some query of the launch has a TSGPU_SORT_VECTOR_QUERY slot: the instantiations with the wave-cooperative distance code (three-key build only)
+    if (vq) hipLaunchKernelGGL((kw_search_kernel<TMAX, CAP, true, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
+    else if (CAP == 512 && !s2) hipLaunchKernelGGL((kw_search_kernel<TMAX, CAP, CAP != 512>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
     else hipLaunchKernelGGL((kw_search_kernel<TMAX, CAP, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
 }
 
 // two-kernel form: find (intersection -> hit records) then score (hit records -> partial top-K)
 template <int TMAX>
 void launch_find_score(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w, const KwPartials& part,
-                       const uint32_t* aux, uint32_t* ids_out, bool s2, uint32_t* hits, const uint64_t* hit_off, hipEvent_t mid_ev = nullptr, bool pair = false, bool plain = false) {
+                       const uint32_t* aux, uint32_t* ids_out, bool s2, uint32_t* hits, const uint64_t* hit_off, hipEvent_t mid_ev = nullptr, bool pair = false, bool plain = false, bool vq = false) {
     if (pair && v.touched) hipLaunchKernelGGL((kw_find2_kernel<TMAX, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);   // the byte-counting instantiation (measurement option)
     else if (pair) hipLaunchKernelGGL((kw_find2_kernel<TMAX>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else hipLaunchKernelGGL((kw_search_kernel<TMAX, 512, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     if (mid_ev) (void)hipEventRecord(mid_ev, s);           // find | score boundary of the batch's first group (tsgpu_timings::kw_find_ms)
-    if (cap == 512 && !s2 && plain && !ids_out) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, false, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
+    if (vq) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_score_kernel<TMAX, decltype(c)::value, true, false, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off); });
+    else if (cap == 512 && !s2 && plain && !ids_out) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, false, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 512 && !s2) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, false>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 512) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 1024) hipLaunchKernelGGL((kw_score_kernel<TMAX, 1024, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
@@ -104,22 +107,26 @@ void launch_find_score(int cap, hipStream_t s, uint32_t n_work, const IndexView&
 
 template <int TMAX>
 void launch_search_mf_cap(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w,
-                          const KwPartials& part, const uint32_t* aux, uint32_t* ids_out) {
-    if (cap == 512) hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 512>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
+                          const KwPartials& part, const uint32_t* aux, uint32_t* ids_out, bool vq = false) {
+    if (vq && cap == 512) hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 512, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
+    else if (vq) hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 1024, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
+    else if (cap == 512) hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 512>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
     else hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 1024>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, (uint32_t*)nullptr, (const uint64_t*)nullptr);
 }
 // two-kernel form of the multi-field search (k + 256 <= 1024 there); oc: queries with filter + excluded ids, counted in id order between the two
 struct MfOrderedCount { const uint32_t* jobs = nullptr; uint32_t n_jobs = 0, table_first = 0; const KwWorkItem* work_all = nullptr; KwPartials part_all{}; };
 template <int TMAX>
 void launch_find_score_mf(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w, const KwPartials& part,
-                          const uint32_t* aux, uint32_t* ids_out, uint32_t* hits, const uint64_t* hit_off, const MfOrderedCount& oc, bool plain = false, int pipelined_lists = 0) {
+                          const uint32_t* aux, uint32_t* ids_out, uint32_t* hits, const uint64_t* hit_off, const MfOrderedCount& oc, bool plain = false, int pipelined_lists = 0, bool vq = false) {
     // pipelined_lists: 2 / 4 = the pipelined find kernel's instantiation that covers every multi-field query of the launch (kw_find_mf2.hip.h); 0 = kw_search_mf_kernel.
     // Same hit records either way.
     if (pipelined_lists == 2) hipLaunchKernelGGL((kw_find_mf2_kernel<TMAX, 2>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else if (pipelined_lists == 4) hipLaunchKernelGGL((kw_find_mf2_kernel<TMAX, 4>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 512, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     if (oc.n_jobs) hipLaunchKernelGGL((kw_mf_ordered_count_kernel<TMAX>), dim3(oc.n_jobs), dim3(64), 0, s, q, oc.work_all, oc.part_all, hits, hit_off, oc.table_first, aux, oc.jobs);
-    if (cap == 512 && plain && !ids_out && !oc.n_jobs) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
+    if (vq && cap == 512) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
+    else if (vq) hipLaunchKernelGGL((kw_score_kernel<TMAX, 1024, true, true, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
+    else if (cap == 512 && plain && !ids_out && !oc.n_jobs) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 512) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else hipLaunchKernelGGL((kw_score_kernel<TMAX, 1024, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
 }
@@ -316,6 +323,7 @@ int tsgpu_sort_key_create_eval(tsgpu_ctx* ctx, const uint32_t* const* ids, const
         good = good && hipGetLastError() == hipSuccess;
     }
     SortKeyDesc d;
+    memset(&d, 0, sizeof d);                   // (form = SORT_KEY_FORM_EVAL: the slot may have held a vector-query key)
     d.dense = dense ? base + at_dense : nullptr;
     d.ids = (const uint32_t*)(base + at_ids);
     d.expr_off = (const uint32_t*)(base + at_off);
@@ -329,6 +337,53 @@ int tsgpu_sort_key_create_eval(tsgpu_ctx* ctx, const uint32_t* const* ids, const
         std::lock_guard<std::mutex> lk(ctx->sk_mu);
         SortKeyHost& k = ctx->sort_keys[handle];
         k.live = true; k.dense = dense; k.buf = buf; k.n_ids = total; k.n_expr = n_expr;
+    }
+    ctx->sort_keys_live.fetch_add(1);
+    *handle_out = handle;
+    return ok();
+}
+
+// ---------------------------------------------------------------- `_vector_query` sort keys (TSGPU_SORT_VECTOR_QUERY)
+int tsgpu_sort_key_create_vector_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* q, float distance_threshold, uint16_t* handle_out) {
+    if (!ctx || !q || !handle_out) return fail(TSGPU_ERR_INVALID, "tsgpu_sort_key_create_vector_query: NULL argument");
+    (void)hipSetDevice(ctx->device);
+    std::lock_guard<std::mutex> mu_lk(ctx->mu);            // the field table and the vector path's stream (the query is staged and normalised there)
+    VecSortView fv;
+    if (const int rc = vec_sort_view(ctx, vec_field_id, &fv, false)) return rc;
+    uint16_t handle;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        if (ctx->sk_free.empty()) return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_sort_key_create_vector_query: every sort-key handle is live (TSGPU_SORT_KEY_SLOTS)");
+        handle = ctx->sk_free.back(); ctx->sk_free.pop_back();                    // (reserved: not live until the upload is done)
+    }
+    DevBuf buf;
+    auto give_back = [&](int rc) {
+        if (buf.p) ctx->retire_bin->put(buf);
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        ctx->sk_free.push_back(handle);
+        return rc;
+    };
+    const size_t bytes = (size_t)fv.dim * 4 + 16;
+    if (hipMalloc(&buf.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.p = nullptr;
+        return give_back(fail(TSGPU_ERR_NO_MEMORY, "tsgpu_sort_key_create_vector_query: device allocation failed"));
+    }
+    buf.cap = bytes;
+    hipStream_t s = ctx->sk_stream;
+    bool good = vec_sort_stage_query(ctx, vec_field_id, q, (float*)buf.p) == TSGPU_OK;      // (cosine: normalised like the k-NN paths' queries; complete on return)
+    // the descriptor names no rows yet (vq_n_rows = 0: every document scores "no row"): the first batch that uses the key fills in the field's state
+    SortKeyDesc d;
+    memset(&d, 0, sizeof d);
+    d.form = SORT_KEY_FORM_VECTOR_QUERY; d.vq_dim = fv.dim; d.vq_q = (const float*)buf.p; d.vq_threshold = distance_threshold; d.vq_ip_lanes = 4;
+    good = good && hipMemcpyAsync(ctx->d_sort_keys.as<SortKeyDesc>() + handle, &d, sizeof d, hipMemcpyHostToDevice, s) == hipSuccess;
+    good = good && hipStreamSynchronize(s) == hipSuccess;
+    if (!good) { (void)hipGetLastError(); return give_back(fail(TSGPU_ERR_DEVICE, "tsgpu_sort_key_create_vector_query: upload failed")); }
+    {
+        std::lock_guard<std::mutex> lk(ctx->sk_mu);
+        SortKeyHost& k = ctx->sort_keys[handle];
+        k = SortKeyHost();
+        k.live = true; k.buf = buf; k.vq = true; k.vq_field = vec_field_id; k.vq_dim = fv.dim; k.vq_threshold = distance_threshold;
     }
     ctx->sort_keys_live.fetch_add(1);
     *handle_out = handle;
@@ -550,6 +605,7 @@ struct Plan {
     uint64_t fbits_words = 0;                             // rank bitmaps of the filtered multi-field queries
     bool any_deadline = false;                            // some query carries a deadline: stamp the batch start, collect cutoff flags
     bool any_s2 = false;              // some query has a third sort key
+    bool any_vq = false;              // some query has a TSGPU_SORT_VECTOR_QUERY slot: the launches take the kernels' VQ instantiations (kw_vq_sort.hip.h)
     bool any_aux = false;             // some query has filter ids, excluded ids or a sort slot of kind >= TSGPU_SORT_EVAL (else the score kernel's PLAIN instantiation serves the batch)
     bool any_array = false;           // some multi-field query has a string[] field
     uint32_t mf_max_fields = 0;       // most query_by fields of any multi-field query (<= 2: the pipelined find kernel, kw_find_mf2.hip.h)
@@ -605,7 +661,7 @@ struct PlanAcc {
     std::vector<uint32_t> aux, ordered_count_q; std::vector<KwQueryMF> mf; std::vector<KwWorkItem> flat_work;
     uint64_t fbits_words = 0, ids_total = 0, list_bytes = 0;
     uint32_t max_k = 0;
-    bool any_deadline = false, any_s2 = false, any_aux = false, any_array = false;
+    bool any_deadline = false, any_s2 = false, any_aux = false, any_array = false, any_vq = false;
     uint32_t mf_max_fields = 0;
 };
 // what the cut needs of a translated query: every token is resolved ONCE, by translate(); the batch chunk is known only after all of them
@@ -768,6 +824,7 @@ struct BatchPlanner {
         if (in.match_type > TSGPU_SUM_SCORE) return refuse(TSGPU_ERR_INVALID);
         uint64_t sort_bytes_per_id = 0;                             // what the sort slots read per ranked document (list_bytes)
         if (const int sort_rc = check_sort_slots(ctx, in.sort, in.n_sort, vflat != nullptr, vflat != nullptr, &sort_bytes_per_id)) return refuse(sort_rc);   // vector_distance belongs to the vector/hybrid entry points
+        for (uint32_t s = 0; s < in.n_sort; s++) if (in.sort[s].kind == TSGPU_SORT_VECTOR_QUERY) A.any_vq = true;      // (keyword and wildcard launches: the kernels' VQ instantiations)
         const uint32_t k = vflat ? std::max<uint32_t>(in.topster_size, 1) : resolve_topster_size(ctx, in);     // (the vector branch resolved it against ITS filter / row count)
         if (k > TSGPU_MAX_TOPK) return refuse(TSGPU_ERR_UNSUPPORTED);
         if (in.deadline_us != 0 && now > in.deadline_us) { P.cutoff[i] = 1; return refuse(TSGPU_ERR_DEADLINE); }
@@ -847,7 +904,7 @@ struct BatchPlanner {
             P.ordered_count_q.insert(P.ordered_count_q.end(), A.ordered_count_q.begin(), A.ordered_count_q.end());
             P.ids_total += A.ids_total; P.fbits_words += A.fbits_words; P.list_bytes += A.list_bytes;
             P.max_k = std::max(P.max_k, A.max_k);
-            P.any_deadline = P.any_deadline || A.any_deadline; P.any_s2 = P.any_s2 || A.any_s2; P.any_aux = P.any_aux || A.any_aux; P.any_array = P.any_array || A.any_array; P.mf_max_fields = std::max(P.mf_max_fields, A.mf_max_fields);
+            P.any_deadline = P.any_deadline || A.any_deadline; P.any_s2 = P.any_s2 || A.any_s2; P.any_aux = P.any_aux || A.any_aux; P.any_vq = P.any_vq || A.any_vq; P.any_array = P.any_array || A.any_array; P.mf_max_fields = std::max(P.mf_max_fields, A.mf_max_fields);
         }
     }
 
@@ -961,7 +1018,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     if ((rc = L.h_plan.reserve((size_t)n_queries * sizeof(KwPlanIn) + 64))) return rc;
     KwPlanIn* hin = (KwPlanIn*)L.h_plan.p;
     const uint32_t n_columns = (uint32_t)ctx->columns.size();
-    std::atomic<int> bad{0}, any_keys{0};
+    std::atomic<int> bad{0}, any_keys{0}, any_vq{0};
     auto scan = [&](uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; i++) {
             const tsgpu_kw_query& in = queries[i];
@@ -970,7 +1027,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
             if (ok) { auto it = snap.field_is_array.find(in.field_ids[0]); ok = it != snap.field_is_array.end() && !it->second; }
             for (uint32_t k = 0; ok && k < in.n_sort; k++)
                 ok = in.sort[k].kind != TSGPU_SORT_VECTOR_DISTANCE && (!sort_kind_reads_column(in.sort[k].kind) || in.sort[k].column < n_columns);
-            for (uint32_t k = 0; ok && k < in.n_sort; k++) if (in.sort[k].kind >= TSGPU_SORT_EVAL) any_keys.store(1, std::memory_order_relaxed);
+            for (uint32_t k = 0; ok && k < in.n_sort; k++) if (in.sort[k].kind >= TSGPU_SORT_EVAL) { any_keys.store(1, std::memory_order_relaxed); if (in.sort[k].kind == TSGPU_SORT_VECTOR_QUERY) any_vq.store(1, std::memory_order_relaxed); }
             ok = ok && check_sort_slots(ctx, in.sort, in.n_sort, false, false, nullptr) == TSGPU_OK;      // (a bad handle, two _eval slots, ...: the host planner reports them per query)
             const uint32_t k = ok ? resolve_topster_size(ctx, in) : 0;
             if (!ok || k > TSGPU_MAX_TOPK) { bad.store(1); return; }
@@ -1036,6 +1093,7 @@ static int plan_batch_device(tsgpu_ctx* ctx, KwLane& L, const Snapshot& snap, co
     P.cutoff.assign(n_queries, 0);
     P.max_k = std::max<uint32_t>(t1.max_k, 1); P.any_s2 = t1.any_s2 != 0; P.list_bytes = t1.list_bytes;
     P.any_aux = any_keys.load() != 0;                  // (a sort-key slot in the batch: the score kernels with the sort-key code)
+    P.any_vq = any_vq.load() != 0;
     DP.on = true;
     DP.dq = dq; DP.dw = dw; DP.daux = (const uint32_t*)(dp + at_aux); DP.hoff = (const uint64_t*)hoff;
     DP.n_work[0] = t1.n_work[0]; DP.n_work[1] = t1.n_work[1]; DP.hit_blocks[0] = t1.hit_blocks[0]; DP.hit_blocks[1] = t1.hit_blocks[1];
@@ -1114,6 +1172,38 @@ void tsgpu_id_lists_free(tsgpu_id_lists* l) { delete l; }
 }  // extern "C"
 
 namespace tsgpu {
+// TSGPU_SORT_VECTOR_QUERY: the descriptor of every live vector-query key the queries name is rewritten from its field as it is NOW (tsgpu_host.h). The caller
+// holds ctx->mu, so no vector mutation and no other batch that reads such a descriptor runs meanwhile; the copies are complete on return, before the batch's
+// kernels are enqueued. Handles that are not live or of the other form are the planner's to refuse (check_sort_slots).
+int refresh_vector_query_keys(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n_queries) {
+    std::vector<uint16_t> done;
+    for (uint32_t i = 0; i < n_queries; i++) {
+        for (uint32_t s = 0; s < queries[i].n_sort && s < TSGPU_MAX_SORT_KEYS; s++) {
+            if (queries[i].sort[s].kind != TSGPU_SORT_VECTOR_QUERY) continue;
+            const uint16_t handle = queries[i].sort[s].column;
+            if (std::find(done.begin(), done.end(), handle) != done.end()) continue;
+            done.push_back(handle);
+            SortKeyDesc d;
+            memset(&d, 0, sizeof d);
+            uint32_t field;
+            {
+                std::lock_guard<std::mutex> lk(ctx->sk_mu);
+                if (handle >= ctx->sort_keys.size() || !ctx->sort_keys[handle].live || !ctx->sort_keys[handle].vq) continue;
+                const SortKeyHost& k = ctx->sort_keys[handle];
+                field = k.vq_field;
+                d.form = SORT_KEY_FORM_VECTOR_QUERY; d.vq_dim = k.vq_dim; d.vq_q = (const float*)k.buf.p; d.vq_threshold = k.vq_threshold;
+            }
+            VecSortView fv;
+            if (const int rc = vec_sort_view(ctx, field, &fv, true)) return rc;
+            d.vq_X = fv.X; d.vq_row_of_seq = fv.row_of_seq; d.vq_row_ok = fv.row_ok; d.vq_n_rows = fv.n_rows; d.vq_map_len = fv.map_len;
+            d.vq_ip_lanes = ctx->vec_ip_lanes;
+            TSGPU_HIP_TRY(hipMemcpyAsync(ctx->d_sort_keys.as<SortKeyDesc>() + handle, &d, sizeof d, hipMemcpyHostToDevice, ctx->sk_stream));
+            TSGPU_HIP_TRY(hipStreamSynchronize(ctx->sk_stream));
+        }
+    }
+    return TSGPU_OK;
+}
+
 struct KwRequest : ParkedRequest {
     const tsgpu_kw_query* q = nullptr;
     tsgpu_hits* out = nullptr;
@@ -1140,6 +1230,13 @@ static int kw_coalesced(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t 
         pending.erase(pending.begin(), pending.begin() + take);
     };
     auto exec = [&](std::vector<KwRequest*>& round, std::unique_ptr<LaneLock>& guard) {
+        // a round with a vector-query sort key runs under ctx->mu (tsgpu_host.h), taken BEFORE the lane like everywhere else: the leader's lane goes back first
+        CtxMuForVectorKeys vq_hold;
+        if (ctx->sort_keys_live.load(std::memory_order_relaxed)) {
+            bool vq = false;
+            for (KwRequest* r : round) vq = vq || names_vector_query_key(r->q, r->units);
+            if (vq) { guard.reset(); vq_hold.take(ctx); guard.reset(new LaneLock(ctx)); vq_hold.stream = guard->L->stream; }
+        }
         KwLane& L = *guard->L;
         int rc = TSGPU_OK;
         std::string err;
@@ -1289,7 +1386,12 @@ static int kw_dispatch(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n
     const bool legacy_keep = ctx->keep_ids;
     if (!wildcard && !legacy_keep && !ids_dev && !present_elsewhere && !tsgpu::tls_no_coalesce() && out->mem == TSGPU_MEM_HOST && n_queries <= ctx->batch_max_queries && ctx->kw_callers.load() > 1)
         return kw_coalesced(ctx, queries, n_queries, out, ids_out);
-    if (!wildcard && !legacy_keep && !ids_out && !present_elsewhere && out->mem == TSGPU_MEM_HOST && ctx->kw_host_split_queries && ctx->n_lanes >= 2 &&
+    // a batch with a vector-query sort key runs under ctx->mu (tsgpu_host.h), taken before its lane; it is served as ONE batch (the slices of a split batch run on
+    // threads of their own)
+    CtxMuForVectorKeys vq_hold;
+    const bool vq = ctx->sort_keys_live.load(std::memory_order_relaxed) != 0 && names_vector_query_key(queries, n_queries);
+    if (vq) vq_hold.take(ctx);
+    if (!vq && !wildcard && !legacy_keep && !ids_out && !present_elsewhere && out->mem == TSGPU_MEM_HOST && ctx->kw_host_split_queries && ctx->n_lanes >= 2 &&
         (uint64_t)n_queries >= 4ull * ctx->kw_host_split_queries)
         return kw_split_host(ctx, queries, n_queries, out);
     std::unique_ptr<tsgpu_id_lists> lists;
@@ -1302,6 +1404,7 @@ static int kw_dispatch(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n
     bo.record_last = legacy_keep;
     bo.present_elsewhere = present_elsewhere;
     LaneLock ll(ctx, legacy_keep ? 0 : (tsgpu::tls_avoid_lane0() ? -2 : -1));          // the legacy "last batch" id API is single-caller: always lane 0
+    vq_hold.stream = ll.L->stream;
     const int rc = kw_batch_on_lane(ctx, *ll.L, queries, n_queries, out, bo);
     if (rc == TSGPU_OK && ids_out) *ids_out = lists.release();
     return rc;
@@ -1563,23 +1666,24 @@ int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap,
                     }
                     const int mf_pipe = !ctx->kw_mf_pipelined ? 0 : (P.mf_max_fields <= 2 ? 2 : (P.mf_max_fields <= 4 ? 4 : 0));
                     if (mf_pipe) ctx->kw_mf_pipelined_launches++;
-                    launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, oc, !P.any_aux && !P.any_array, mf_pipe);
+                    launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, oc, !P.any_aux && !P.any_array, mf_pipe, P.any_vq);
                 }
                 else {
                     const bool mark = !st.find_marked;
                     st.find_marked = true;
-                    launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux);
+                    launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux, P.any_vq);
                 }
             }
-        } else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out);
-        else with_cap(cap, [&](auto c) { launch_search<TM, decltype(c)::value>(s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_s2); });
+        } else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_vq);
+        else with_cap(cap, [&](auto c) { launch_search<TM, decltype(c)::value>(s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_s2, P.any_vq); });
     };
     run_table(0, std::integral_constant<int, 3>(), std::false_type());
     run_table(1, std::integral_constant<int, KW_MAX_TOKENS>(), std::false_type());
     run_table(2, std::integral_constant<int, 3>(), std::true_type());
     run_table(3, std::integral_constant<int, KW_MAX_TOKENS>(), std::true_type());
     const size_t sh = H.first[4];
-    if (H.n[4]) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
+    if (H.n[4] && P.any_vq) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value, true>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
+    else if (H.n[4]) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
     if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[1], s));
     if (!P.groups.empty()) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_merge_groups_kernel<decltype(c)::value>), dim3((uint32_t)P.groups.size()), dim3(KW_THREADS), 0, s, dq, T.part, T.groups); });
     with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_merge_kernel<decltype(c)::value>), dim3(n_queries), dim3(KW_THREADS), 0, s, dq, T.part, T.o, ids_out, dw, ctx->kw_merge_select_min); });
@@ -1746,6 +1850,11 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
     const bool keep_ids = bo.keep_ids || bo.id_lists != nullptr;
     hipStream_t s = L.stream;
     SliceChain::Turn chain_turn(bo.chain, bo.chain_index);     // (passes the turn on when this slice leaves, whatever happens to it)
+    if (ctx->sort_keys_live.load(std::memory_order_relaxed) && names_vector_query_key(queries, n_queries)) {
+        // vector-query sort keys read their field as it is now; whoever sent the batch here took ctx->mu for it (kw_dispatch, kw_coalesced, the candidates and grouped calls)
+        if (!tls_holds_ctx_mu()) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_keyword_search_batch: a vector-query sort key on a path that does not hold the index lock");
+        if (const int rc = refresh_vector_query_keys(ctx, queries, n_queries)) return rc;
+    }
     try {
         static const bool host_timing = getenv("TSGPU_HOST_TIMING") != nullptr;      // diagnostics: host phases of the call on stderr
         const uint64_t t_enter = now_us();
@@ -1954,10 +2063,13 @@ int kw_candidates_batch_ex(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
     const bool dev_out = out->mem == TSGPU_MEM_DEVICE;
     if (dev_out && (!out->text_match || !out->vector_distance || !out->match_score_index || !out->num_matched))
         return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_search_candidates_batch: device output needs every tsgpu_hits array");
+    CtxMuForVectorKeys vq_hold;                       // combinations with a vector-query sort key: ctx->mu before the lane, until the kernels have finished (tsgpu_host.h)
+    if (ctx->sort_keys_live.load(std::memory_order_relaxed) && names_vector_query_key(combos, n_combos)) vq_hold.take(ctx);
     LaneLock ll(ctx, 0);                              // (tsgpu_candidates_result_ids reads this lane's bitmaps afterwards)
     KwLane& L = *ll.L;
     (void)hipSetDevice(ctx->device);
     hipStream_t s = L.stream;
+    vq_hold.stream = s;
     try {
         int rc;
         const size_t pslots = (size_t)std::max<uint32_t>(n_combos, 1) * KS, pn = std::max<uint32_t>(n_combos, 1);

@@ -119,6 +119,11 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
     static const bool host_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
     const uint64_t t_enter = now_us();
     const uint32_t n_combos = cfirst[n_queries];
+    // vector-query sort keys (TSGPU_SORT_VECTOR_QUERY) read their field as it is now: the lock their batches need is the one held here — the nested id pass
+    // is told so — and the scoring kernels below read the descriptors this writes
+    tsgpu::CtxMuHeld mu_held;
+    if (ctx->sort_keys_live.load(std::memory_order_relaxed) && tsgpu::names_vector_query_key(combos, n_combos))
+        if (const int rc = tsgpu::refresh_vector_query_keys(ctx, combos, n_combos)) return rc;
     try {
         std::vector<int32_t> status(n_queries, TSGPU_OK), cutoff(n_queries, 0);
         std::vector<uint64_t> num_matched(n_queries, 0);
@@ -386,7 +391,10 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             if (any_iota) hipLaunchKernelGGL(gb_iota_kernel, dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, a);
             uint32_t max_lists = 0;
             for (uint32_t i = 0; i < n_queries; i++) if (gq[i].run) for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; c++) max_lists = std::max(max_lists, qd[c].n_lists);
-            if (max_lists <= 3) hipLaunchKernelGGL((gb_score_kernel<3>), dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, v, a);
+            const bool vq = tsgpu::names_vector_query_key(combos, n_combos);      // the instantiations with the wave-cooperative distance code (kw_vq_sort.hip.h)
+            if (max_lists <= 3 && vq) hipLaunchKernelGGL((gb_score_kernel<3, true>), dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, v, a);
+            else if (vq) hipLaunchKernelGGL((gb_score_kernel<KW_MAX_TOKENS, true>), dim3((uint32_t)(n_blocks * (GB_THREADS / 64))), dim3(64), 0, s, v, a);
+            else if (max_lists <= 3) hipLaunchKernelGGL((gb_score_kernel<3>), dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, v, a);
             else hipLaunchKernelGGL((gb_score_kernel<KW_MAX_TOKENS>), dim3((uint32_t)(n_blocks * (GB_THREADS / 64))), dim3(64), 0, s, v, a);
             if (any_dedupe) hipLaunchKernelGGL(gb_dedupe_kernel, dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, a);
             hipLaunchKernelGGL(gb_insert_kernel, dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, a);

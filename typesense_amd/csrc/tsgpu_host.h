@@ -31,6 +31,8 @@ namespace tsgpu {
 inline std::string& tls_error() { static thread_local std::string e; return e; }
 inline bool& tls_no_coalesce() { static thread_local bool b = false; return b; }     // this thread's keyword batches go to a lane directly, never into the combiner of the 1-query
                                                                                       // callers (a grouped call's nested id pass holds ctx->mu: it must not park there)
+inline bool& tls_holds_ctx_mu() { static thread_local bool b = false; return b; }     // this thread holds ctx->mu (a grouped call around its nested id pass; a batch that names a
+                                                                                      // vector-query sort key, CtxMuForVectorKeys): such a batch must not lock it again
 inline bool& tls_avoid_lane0() { static thread_local bool b = false; return b; }      // this thread's keyword batches keep off lane 0 (it shares the vector path's stream)
 inline int fail(int code, const std::string& msg) { tls_error() = msg; return code; }
 inline int ok() { return TSGPU_OK; }
@@ -305,7 +307,9 @@ struct Snapshot {            // immutable view of all posting lists; published b
 
 // One live `_eval` sort key (tsgpu_sort_key_create_eval): its device allocation — [scores | expr_off | ids | dense bytes], described to the kernels by the
 // SortKeyDesc at its handle's slot of ctx->d_sort_keys — and what the planner's byte accounting needs.
-struct SortKeyHost { bool live = false, dense = false; DevBuf buf; uint64_t n_ids = 0; uint32_t n_expr = 0; };
+// A `_vector_query` key (tsgpu_sort_key_create_vector_query; vq = true) holds its query vector in buf and NAMES its vector field: the rest of its descriptor
+// is written by every batch that uses it (refresh_vector_query_keys, under ctx->mu), from the field as it is then.
+struct SortKeyHost { bool live = false, dense = false; DevBuf buf; uint64_t n_ids = 0; uint32_t n_expr = 0; bool vq = false; uint32_t vq_field = 0, vq_dim = 0; float vq_threshold = 0; };
 
 struct ColumnDev { DevBuf data; uint32_t n = 0; std::vector<int64_t> host; /* mirror for the <=k-hit host steps (vector / hybrid) */ };
 
@@ -626,17 +630,18 @@ struct tsgpu_ctx {
 // the vector / hybrid entry points, which refuse the kinds beyond TSGPU_SORT_VECTOR_DISTANCE)
 namespace tsgpu {
 inline bool sort_kind_reads_column(uint8_t kind) { return kind == TSGPU_SORT_INT64_COLUMN || (kind >= TSGPU_SORT_INT64_COLUMN_MISSING_FIRST && kind <= TSGPU_SORT_STRING_RANK_FLIP); }
-inline bool sort_kind_reads_key(uint8_t kind) { return kind == TSGPU_SORT_EVAL || sort_kind_reads_column(kind); }
-// TSGPU_OK, 400 (a TSGPU_SORT_EVAL slot whose handle is not live) or 501 (a kind / column / order this path does not serve; two _eval slots). allow_vdist: the flat
-// vector branch; refuse_keys: an entry point that does not serve kinds >= TSGPU_SORT_EVAL (so does every context that is a member of a tsgpu_group: a key is
-// one context's). bytes_per_id (nullable): what the slots read per ranked document — 8 per column value, 1 per dense-key byte, 4 x probes per sparse key.
+inline bool sort_kind_reads_key(uint8_t kind) { return kind == TSGPU_SORT_EVAL || kind == TSGPU_SORT_VECTOR_QUERY || sort_kind_reads_column(kind); }
+// TSGPU_OK, 400 (a TSGPU_SORT_EVAL / _VECTOR_QUERY slot whose handle is not live or belongs to a key of the other form) or 501 (a kind / column / order this path
+// does not serve; two _eval slots). allow_vdist: the flat vector branch; refuse_keys: an entry point that does not serve kinds >= TSGPU_SORT_EVAL (so does every
+// context that is a member of a tsgpu_group: a key is one context's). bytes_per_id (nullable): what the slots read per ranked document — 8 per column value,
+// 1 per dense-key byte, 4 x probes per sparse key, 4 x dim per vector-query key.
 inline int check_sort_slots(tsgpu_ctx* ctx, const tsgpu_sort_by* sort, uint32_t n_sort, bool allow_vdist, bool refuse_keys, uint64_t* bytes_per_id) {
     uint32_t n_eval = 0;
     uint64_t bytes = 0;
     int rc = TSGPU_OK;
     for (uint32_t s = 0; s < n_sort; s++) {
         const uint8_t kind = sort[s].kind;
-        if (kind > TSGPU_SORT_STRING_RANK_FLIP) return TSGPU_ERR_UNSUPPORTED;
+        if (kind > TSGPU_SORT_VECTOR_QUERY || (kind > TSGPU_SORT_STRING_RANK_FLIP && kind < TSGPU_SORT_VECTOR_QUERY)) return TSGPU_ERR_UNSUPPORTED;      // (8 is no kind)
         if (kind == TSGPU_SORT_VECTOR_DISTANCE && !allow_vdist) return TSGPU_ERR_UNSUPPORTED;
         if (kind >= TSGPU_SORT_EVAL && (refuse_keys || ctx->group_member.load(std::memory_order_relaxed) > 0)) return TSGPU_ERR_UNSUPPORTED;
         if (sort[s].order != 1 && sort[s].order != -1) return TSGPU_ERR_UNSUPPORTED;
@@ -647,7 +652,7 @@ inline int check_sort_slots(tsgpu_ctx* ctx, const tsgpu_sort_by* sort, uint32_t 
         if (kind == TSGPU_SORT_EVAL) {
             n_eval++;
             std::lock_guard<std::mutex> lk(ctx->sk_mu);
-            if (sort[s].column >= ctx->sort_keys.size() || !ctx->sort_keys[sort[s].column].live) rc = TSGPU_ERR_INVALID;
+            if (sort[s].column >= ctx->sort_keys.size() || !ctx->sort_keys[sort[s].column].live || ctx->sort_keys[sort[s].column].vq) rc = TSGPU_ERR_INVALID;
             else {
                 const SortKeyHost& k = ctx->sort_keys[sort[s].column];
                 uint32_t probes = 1;
@@ -655,12 +660,48 @@ inline int check_sort_slots(tsgpu_ctx* ctx, const tsgpu_sort_by* sort, uint32_t 
                 bytes += k.dense ? 1 : 4ull * probes * k.n_expr;
             }
         }
+        if (kind == TSGPU_SORT_VECTOR_QUERY) {
+            std::lock_guard<std::mutex> lk(ctx->sk_mu);
+            if (sort[s].column >= ctx->sort_keys.size() || !ctx->sort_keys[sort[s].column].live || !ctx->sort_keys[sort[s].column].vq) rc = TSGPU_ERR_INVALID;
+            else bytes += 4ull * ctx->sort_keys[sort[s].column].vq_dim;
+        }
     }
     if (n_eval > 1) return TSGPU_ERR_UNSUPPORTED;          // (the reference shares one cursor vector between them, src/index.cpp:5809-5811)
     if (bytes_per_id) *bytes_per_id = bytes;
     return rc;
 }
 }  // namespace tsgpu
+
+// ---- TSGPU_SORT_VECTOR_QUERY: a keyword batch reads a vector field's rows (kw_vq_sort.hip.h). A key reads the field AS IT IS WHEN THE BATCH RUNS, and no
+// kernel may read a row matrix an upsert has released: such a batch holds ctx->mu — the mutex every vector mutation takes — from before it acquires its lane
+// (the grouped calls take the mutex first and a lane second: the same order everywhere) until its kernels have finished. Batches without such a slot lock nothing.
+namespace tsgpu {
+inline bool names_vector_query_key(const tsgpu_kw_query* queries, uint32_t n_queries) {
+    for (uint32_t i = 0; i < n_queries; i++)
+        for (uint32_t s = 0; s < queries[i].n_sort && s < TSGPU_MAX_SORT_KEYS; s++) if (queries[i].sort[s].kind == TSGPU_SORT_VECTOR_QUERY) return true;
+    return false;
+}
+struct CtxMuForVectorKeys {
+    tsgpu_ctx* ctx = nullptr;
+    hipStream_t stream = nullptr;                    // set once the batch has its lane: what must have finished before the mutex is released
+    void take(tsgpu_ctx* c) { if (ctx || tls_holds_ctx_mu()) return; c->mu.lock(); ctx = c; tls_holds_ctx_mu() = true; }
+    ~CtxMuForVectorKeys() {
+        if (!ctx) return;
+        if (stream && hipStreamSynchronize(stream) != hipSuccess) (void)hipGetLastError();
+        tls_holds_ctx_mu() = false;
+        ctx->mu.unlock();
+    }
+};
+// RAII for a scope that holds ctx->mu by other means (std::lock_guard) and runs keyword batches inside
+struct CtxMuHeld { bool old; CtxMuHeld() : old(tls_holds_ctx_mu()) { tls_holds_ctx_mu() = true; } ~CtxMuHeld() { tls_holds_ctx_mu() = old; } };
+// what a vector-query key's descriptor takes from its field (tsgpu_vec.hip; caller holds ctx->mu): the device row map is rebuilt when the field's labels changed
+struct VecSortView { const float* X; const uint32_t* row_of_seq; const uint8_t* row_ok; uint32_t n_rows, map_len, dim; int metric; };
+int vec_sort_view(tsgpu_ctx* ctx, uint32_t vec_field_id, VecSortView* out, bool with_map);
+// copies a key's query (host, dim floats) to dst_dev and normalises it for a cosine field, as stage_queries does for the k-NN paths; caller holds ctx->mu
+int vec_sort_stage_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* q, float* dst_dev);
+// every live vector-query key the queries name gets its descriptor rewritten from its field; caller holds ctx->mu (tsgpu.hip)
+int refresh_vector_query_keys(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n_queries);
+}
 
 // ---- device-side halves of tsgpu_group's exchange (tsgpu_group.hip orchestrates; kernels: kw_kernels.hip.h / vec_kernels.hip.h).
 // All of them ENQUEUE on `s` and do not synchronise. A keyword exchange block = n_q records of k * words + 3 u64 (KwShardIn::packed),

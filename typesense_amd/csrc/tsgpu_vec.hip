@@ -31,6 +31,11 @@ struct VecField {
     bool identity = true;                              // label == row for every row so far
     std::unordered_map<uint64_t, uint32_t> row_of;     // materialised when identity breaks
     bool any_deleted = false;
+    // seq_id -> row for the keyword kernels' vector-query sort slot (vec_sort_view): a device array over [0, max label], 0xFFFFFFFF = none; identity fields need none.
+    // label_version counts the calls that may have changed row_of; the array is rebuilt when it lags behind
+    DevBuf d_row_of_seq;
+    uint32_t row_of_seq_len = 0;
+    uint64_t label_version = 1, row_of_seq_version = 0;
     // scratch
     DevBuf d_dense, d_cand, d_cand_cnt, d_tau, dQ, d_dist, d_lab, d_cnt, d_mask, d_rows, d_q1, d_out1;
     DevBuf d_Qh, d_cq, d_L1, d_lbkey, d_surv, d_surv_cnt, d_gkeys;
@@ -59,7 +64,7 @@ struct VecField {
         identity = false;
     }
     void release() {
-        DevBuf* b[] = {&X, &labels, &row_ok, &Xh, &xnorm, &tile_nmax, &d_dense, &d_cand, &d_cand_cnt, &d_tau, &dQ, &d_dist, &d_lab, &d_cnt, &d_mask, &d_rows,
+        DevBuf* b[] = {&X, &labels, &row_ok, &Xh, &xnorm, &tile_nmax, &d_row_of_seq, &d_dense, &d_cand, &d_cand_cnt, &d_tau, &dQ, &d_dist, &d_lab, &d_cnt, &d_mask, &d_rows,
                        &d_q1, &d_out1, &d_Qh, &d_cq, &d_L1, &d_lbkey, &d_surv, &d_surv_cnt, &d_gkeys, &d_qbits, &d_qoff, &d_frows, &d_fptr, &d_perm, &d_Qperm, &d_pdist, &d_plab, &d_pcnt, &g_link0, &g_upper_ptr, &g_upper_links, &g_visited, &g_vhash, &g_stat, &g_sel};
         for (auto* x : b) x->release();
     }
@@ -708,6 +713,7 @@ int tsgpu_vec_upsert(tsgpu_ctx* ctx, uint32_t vec_field_id, const uint64_t* labe
     (void)hipSetDevice(ctx->device);
     VecField* f = get_field(ctx, vec_field_id);
     if (!f) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_vec_upsert: unknown vector field");
+    f->label_version++;                             // (whatever this call does to the label map: the device copy of it is rebuilt by the next batch that reads it)
     hipStream_t s = ctx->stream;
     try {
         std::vector<uint64_t> hl(n);
@@ -850,6 +856,42 @@ uint64_t tsgpu_vec_count(tsgpu_ctx* ctx, uint32_t vec_field_id) {
 }  // extern "C"
 
 namespace tsgpu {
+// ---- the keyword kernels' vector-query sort slot (TSGPU_SORT_VECTOR_QUERY; tsgpu_host.h, kw_vq_sort.hip.h). Caller holds ctx->mu.
+int vec_sort_view(tsgpu_ctx* ctx, uint32_t vec_field_id, VecSortView* out, bool with_map) {
+    VecField* f = get_field(ctx, vec_field_id);
+    if (!f) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_sort_key_create_vector_query: unknown vector field");
+    (void)hipSetDevice(ctx->device);
+    out->X = f->X.as<float>(); out->row_ok = f->row_ok.as<uint8_t>(); out->n_rows = (uint32_t)f->n_rows; out->dim = f->dim; out->metric = f->metric;
+    out->row_of_seq = nullptr; out->map_len = 0;
+    if (!with_map || f->identity) return TSGPU_OK;                  // identity numbering: row = seq_id while seq_id < n_rows
+    if (f->row_of_seq_version != f->label_version) {
+        try {
+            uint64_t len = 0;                                       // labels >= 2^32 are no seq_ids: they never match
+            for (const auto& e : f->row_of) if (e.first < 0xFFFFFFFFull) len = std::max<uint64_t>(len, e.first + 1);
+            std::vector<uint32_t> map((size_t)len, 0xFFFFFFFFu);
+            for (const auto& e : f->row_of) if (e.first < len) map[(size_t)e.first] = e.second;
+            int rc;
+            if ((rc = f->d_row_of_seq.reserve(std::max<size_t>((size_t)len * 4, 16)))) return rc;
+            if (len) TSGPU_HIP_TRY(hipMemcpy(f->d_row_of_seq.p, map.data(), (size_t)len * 4, hipMemcpyHostToDevice));
+            f->row_of_seq_len = (uint32_t)len;
+            f->row_of_seq_version = f->label_version;
+        } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "vector-query sort key: host allocation failed"); }
+    }
+    out->row_of_seq = f->d_row_of_seq.as<uint32_t>(); out->map_len = f->row_of_seq_len;
+    return TSGPU_OK;
+}
+int vec_sort_stage_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* q, float* dst_dev) {
+    VecField* f = get_field(ctx, vec_field_id);
+    if (!f) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_sort_key_create_vector_query: unknown vector field");
+    hipStream_t s = ctx->stream;
+    TSGPU_HIP_TRY(hipMemcpyAsync(dst_dev, q, (size_t)f->dim * 4, hipMemcpyHostToDevice, s));
+    if (f->metric == TSGPU_METRIC_COSINE)               // src/collection.cpp:1445-1448 (hnsw_index_t::normalize_vector)
+        hipLaunchKernelGGL(vec_normalize_rows_kernel, dim3(1), dim3(64), 0, s, dst_dev, 1u, f->dim);
+    TSGPU_HIP_TRY(hipGetLastError());
+    TSGPU_HIP_TRY(hipStreamSynchronize(s));
+    return TSGPU_OK;
+}
+
 struct VecRequest : ParkedRequest {
     uint32_t field = 0, k = 0;
     const float* Q = nullptr;                        // host, [units][dim]

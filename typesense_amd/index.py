@@ -229,6 +229,19 @@ class GpuIndex:
         self._sort_keys.add(int(handle.value))
         return int(handle.value)
 
+    def sort_key_create_vector_query(self, field_id, q, distance_threshold=None):
+        """the key of a `_vector_query(field:([...]))` sort slot (B.SORT_VECTOR_QUERY): q = the query vector (the field's dim floats; normalised by the
+        library for a cosine field), distance_threshold = None for none. The key names its field: searches read the field's rows as they are then."""
+        dim = self.vec_dim.get(field_id)
+        v = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+        if dim is not None and v.size != dim:
+            raise ValueError("the query vector must have the field's %d dimensions" % dim)
+        handle = C.c_uint16(0)
+        thr = B.FLT_MAX if distance_threshold is None else float(distance_threshold)
+        self._ck(self.L.tsgpu_sort_key_create_vector_query(self.h, field_id, _vp(v), C.c_float(thr), C.byref(handle)))
+        self._sort_keys.add(int(handle.value))
+        return int(handle.value)
+
     def sort_key_destroy(self, handle):
         self._ck(self.L.tsgpu_sort_key_destroy(self.h, int(handle)))
         self._sort_keys.discard(int(handle))
