@@ -157,6 +157,8 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
  * (identical result sets either way), "vec_count_rescored" = 1: keep the vec_rescored_rows and vec_candidate_rows counters (costs two syncs);
  * "vec_filter_direct_max" = 0 .. 65536 (default 65536): tsgpu_vec_knn_batch_filtered re-scores the rows of an allow list of at most this many ids
  * directly instead of scanning (0 = every filtered query goes through the masked scan; identical results either way);
+ * "vec_flat_group_max_bytes" = 4 .. 2^30 (default 2^30): bytes of the ragged distance array ONE launch of tsgpu_vector_search_batch_per_query's flat
+ * queries fills; a batch whose segments exceed it is split into consecutive groups of queries (tests lower it to force the split; identical results);
  * micro-batcher: "batch_max_queries" = calls with at most this many queries are coalesced with concurrent callers (default 64,
  * 0 = never), "batch_window_us" = how long a round's leader waits for the other threads that are inside the entry point to
  * park (default 10: a lane that is free should not idle; while every lane is busy callers keep parking and the rounds size
@@ -193,6 +195,7 @@ int tsgpu_set_stream(tsgpu_ctx* ctx, void* hip_stream);
 int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
 /* introspection counters (tests / bench): "vec_overflow_rounds", "vec_prefilter_groups", "vec_prefilter_fallbacks",
  * "vec_filter_direct_queries" / "vec_filter_scan_queries" (filtered queries of tsgpu_vec_knn_batch_filtered answered by either route),
+ * "vec_search_pq_flat_queries" / "vec_search_pq_kcut_queries" / "vec_search_pq_flat_lists" / "vec_search_pq_flat_launches" (tsgpu_vector_search_batch_per_query, cumulative),
  * "vec_filter_h2d_bytes" (bytes of id lists uploaded for them), "vec_filter_stage_us" / "vec_filter_build_us" (host time staging and uploading the lists / time of the
  * bitmap and survivor-list build kernels; both kept under "vec_count_rescored"),
  * "vec_rescored_rows", "vec_candidate_rows" (rows of the last bracket group that reached the exact re-score / that passed the scan's tile-level bound),
@@ -546,8 +549,8 @@ int tsgpu_vec_knn_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const float* Q, i
  * n_out); deleted rows are never returned, unknown labels in a list are ignored. Allow lists of at most "vec_filter_direct_max" ids are
  * re-scored directly, the other queries share one masked scan. Small host-to-host calls from concurrent threads are coalesced exactly like
  * tsgpu_vec_knn_batch's, and with them ("batch_max_queries"); tsgpu_hybrid_search_batch's vector pass is such a call. The HNSW search takes the same
- * filters (tsgpu_vec_hnsw_search_batch_filtered). Not covered (they keep one pass per filtered query): tsgpu_vector_search_batch's single parameter
- * block, the tsgpu_group_* shard forms; filters must be host lists. */
+ * filters (tsgpu_vec_hnsw_search_batch_filtered), and the pure vector search has its per-query form on top of this one
+ * (tsgpu_vector_search_batch_per_query). Not covered (they keep one pass per filtered query): the tsgpu_group_* shard forms; filters must be host lists. */
 typedef struct tsgpu_vec_filter {
     uint32_t filtered;              /* 0 = no allow list (all live rows); 1 = only allow_ids (n_allow == 0: nothing) */
     uint32_t n_allow;
@@ -672,6 +675,29 @@ int tsgpu_vector_search_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu
  * *ids_out is a list object the caller frees with tsgpu_id_lists_free (tsgpu_id_lists_ids / tsgpu_id_lists_count per query) */
 int tsgpu_vector_search_batch_ids(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params,
                                   const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out, tsgpu_id_lists** ids_out);
+/* The same search with ONE PARAMETER BLOCK PER QUERY (the server's calling convention: every request brings its own filter_by, k, threshold, sort,
+ * flat_search_cutoff and query_doc): params[i] belongs to Q[i]. Query i answers exactly as tsgpu_vector_search_batch[_ids] does for Q[i] alone with
+ * params[i] — keys in order, all three scores, vector_distance bits, match_score_index, n_hits, num_matched, search_cutoff, its id list — and picks its
+ * own branch by the same rule (n_filter != 0 && n_filter < flat_search_cutoff -> FLAT).
+ *   k-cut queries run as ONE tsgpu_vec_knn_batch_filtered at K = the largest k of them (after the query_doc increment); query i keeps the first k_i
+ *     results: the result order (distance, then smaller label) is total and a pair's distance does not depend on k. The finishing (label order, query_doc,
+ *     abs(), threshold, sort scores, Topster) is the single call's, on the host.
+ *   FLAT queries: distinct lists are recognised by (pointer, length), need not be adjacent, and are translated and uploaded once each; ONE launch of
+ *     vec_flat_ragged_distances_kernel fills one ragged distance array (query i's segment aligned with its list; its query document is a per-query
+ *     argument, so queries sharing a list may name different documents), ONE ranking call ranks every segment. The distance launch is split into
+ *     consecutive groups of queries whose segments fit "vec_flat_group_max_bytes" (1 GiB; one launch per group, the array itself stays whole).
+ * What the single call refuses as a call for reasons that lie in the parameter block is query i's status[i] here, with n_hits[i] = 0 and an empty id
+ * list, and the other queries are answered: more than 3 sort keys, k and fetch_size both 0, a NULL id array with a non-zero count, k_stride too small for
+ * that query (400); a sort kind >= TSGPU_SORT_EVAL, k > TSGPU_MAX_TOPK (501). Failures of the call: NULL arguments, unknown field, missing output arrays,
+ * out->mem != TSGPU_MEM_HOST (501: host outputs only; Q may be in device memory — it is copied to the host once).
+ * Counters (cumulative): "vec_search_pq_flat_queries", "vec_search_pq_kcut_queries", "vec_search_pq_flat_lists" (distinct lists uploaded),
+ * "vec_search_pq_flat_launches" (ragged distance launches).
+ * Not covered: coalescing one-query calls of tsgpu_vector_search_batch (they keep one pass each), the tsgpu_group_* shard forms, device-memory outputs,
+ * sort kinds >= TSGPU_SORT_EVAL, filter lists that already live on the device, the k-cut finishing on the device. */
+int tsgpu_vector_search_batch_per_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params /* [n_q] */,
+                                        const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out);
+int tsgpu_vector_search_batch_per_query_ids(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params /* [n_q] */,
+                                            const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out, tsgpu_id_lists** ids_out);
 
 /* ------------------------------------------------------------------ hybrid (B3) */
 typedef struct tsgpu_hybrid_params {

@@ -487,6 +487,11 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
         ctx->vec_filter_direct_max = (uint32_t)value;
         return ok();
     }
+    if (!strcmp(name, "vec_flat_group_max_bytes")) {    // cap of the ragged distance array one launch fills (tsgpu_vector_search_batch_per_query); only lowered (tests: the split at a small shape)
+        if (value < 4 || value > (1ll << 30)) return fail(TSGPU_ERR_INVALID, "vec_flat_group_max_bytes out of range (4 .. 1 GiB)");
+        ctx->vec_flat_group_max_bytes = (uint64_t)value;
+        return ok();
+    }
     // micro-batcher (tsgpu_batcher.h): concurrent small calls are coalesced into one launch
     if (!strcmp(name, "index_min_slack_words")) { ctx->index_min_slack_words = (uint64_t)std::max<int64_t>(value, 0); return ok(); }   // (tests: small arenas)
     if (!strcmp(name, "index_compact_min_words")) { ctx->index_compact_min_words = (uint64_t)std::max<int64_t>(value, 0); return ok(); }   // (tests: small arenas)
@@ -529,6 +534,10 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "vec_prefilter_groups")) { *out = ctx->vec_prefilter_groups; return ok(); }
     if (!strcmp(name, "vec_filter_direct_queries")) { *out = ctx->vec_filter_direct_queries; return ok(); }
     if (!strcmp(name, "vec_filter_scan_queries")) { *out = ctx->vec_filter_scan_queries; return ok(); }
+    if (!strcmp(name, "vec_search_pq_flat_queries")) { *out = ctx->vec_search_pq_flat_queries.load(); return ok(); }     // tsgpu_vector_search_batch_per_query, cumulative
+    if (!strcmp(name, "vec_search_pq_kcut_queries")) { *out = ctx->vec_search_pq_kcut_queries.load(); return ok(); }
+    if (!strcmp(name, "vec_search_pq_flat_lists")) { *out = ctx->vec_search_pq_flat_lists.load(); return ok(); }         // distinct flat lists uploaded
+    if (!strcmp(name, "vec_search_pq_flat_launches")) { *out = ctx->vec_search_pq_flat_launches.load(); return ok(); }   // launches of vec_flat_ragged_distances_kernel
     if (!strcmp(name, "vec_filter_h2d_bytes")) { *out = ctx->vec_filter_h2d_bytes; return ok(); }
     if (!strcmp(name, "vec_filter_stage_us")) { *out = ctx->vec_filter_stage_us; return ok(); }
     if (!strcmp(name, "vec_filter_build_us")) { *out = ctx->vec_filter_build_us; return ok(); }
@@ -698,11 +707,12 @@ struct BatchPlanner {
         q.n_excl = in.n_excluded;
         q.n_filt = in.n_filter;
         if (vflat) {
-            // flat vector branch: query i ranks ITS row of the distance matrix (aligned with the filter ids); the queries of a call share
-            // one filter (same host array): uploaded once per planning slice
+            // flat vector branch: query i ranks ITS row of the distance matrix (aligned with the filter ids) — or its segment of a ragged array, with its
+            // own threshold; neighbouring queries that pass the same host array share one upload of it per planning slice (the per-query entry point
+            // orders its flat queries by list)
             if (in.n_excluded || !in.n_filter) { P.status[i] = TSGPU_ERR_INVALID; return; }
-            q.vdist = (uint64_t)(uintptr_t)(vflat->dist_dev + (size_t)i * vflat->stride);
-            q.vdist_thr = vflat->threshold; q.vdist_abs = vflat->abs ? 1 : 0;
+            q.vdist = (uint64_t)(uintptr_t)(vflat->dist_dev + (vflat->off ? (size_t)vflat->off[i] : (size_t)i * vflat->stride));
+            q.vdist_thr = vflat->thr ? vflat->thr[i] : vflat->threshold; q.vdist_abs = vflat->abs ? 1 : 0;
         }
         if (vflat && i > lo && P.status[i - 1] == TSGPU_OK && queries[i - 1].filter_ids == in.filter_ids && queries[i - 1].n_filter == in.n_filter) q.aux_off = P.q[i - 1].aux_off;
         else {

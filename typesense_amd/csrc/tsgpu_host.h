@@ -589,6 +589,9 @@ struct tsgpu_ctx {
     uint64_t vec_prefilter_groups = 0;               // query groups answered by the bf16 bracket path
     uint32_t vec_filter_direct_max = 65536;          // tsgpu_vec_knn_batch_filtered: allow lists of at most this many ids skip the scan (re-scored directly); 0 = every filtered query is scanned
     uint64_t vec_filter_direct_queries = 0, vec_filter_scan_queries = 0;   // counters: filtered queries answered by either route
+    // tsgpu_vector_search_batch_per_query (cumulative; calls run concurrently): queries answered by either branch, distinct flat lists uploaded, ragged launches
+    std::atomic<uint64_t> vec_search_pq_flat_queries{0}, vec_search_pq_kcut_queries{0}, vec_search_pq_flat_lists{0}, vec_search_pq_flat_launches{0};
+    uint64_t vec_flat_group_max_bytes = 1ull << 30;  // ... bytes of the ragged distance array ONE launch of it fills (option; tests lower it to force the split)
     uint64_t vec_filter_h2d_bytes = 0;               // counter: bytes of id lists (+ their offsets) uploaded for per-query filters
     uint64_t vec_filter_stage_us = 0, vec_filter_build_us = 0;   // counters: host time staging + uploading the lists / time of the bitmap or survivor-list build kernels that follow (only under vec_count_rescored: it costs a sync per group)
     int hnsw_test_tiny_cand = 0;                      // TESTS ONLY (option "hnsw_test_tiny_cand"): searches with max(ef, k) <= 128 start on a 24-entry candidate heap, so that
@@ -707,8 +710,9 @@ int refresh_vector_query_keys(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uin
 // All of them ENQUEUE on `s` and do not synchronise. A keyword exchange block = n_q records of k * words + 3 u64 (KwShardIn::packed),
 // a k-NN block = n_q * k u64 (vec_group_pack_kernel).
 namespace tsgpu {
-// flat vector branch (tsgpu_vec.hip -> tsgpu.hip): query i ranks row i of a device distance matrix aligned with its filter ids
-struct KwVFlat { const float* dist_dev; size_t stride; float threshold; bool abs; };
+// flat vector branch (tsgpu_vec.hip -> tsgpu.hip): query i ranks row i of a device distance matrix aligned with its filter ids; with `off` the array is
+// RAGGED (tsgpu_vector_search_batch_per_query): query i's segment starts at dist_dev + off[i] and is aligned with ITS filter ids, its threshold is thr[i]
+struct KwVFlat { const float* dist_dev; size_t stride; float threshold; bool abs; const uint64_t* off = nullptr; const float* thr = nullptr; };
 int kw_vector_flat_search(tsgpu_ctx* ctx, const tsgpu_kw_query* queries, uint32_t n_queries, tsgpu_hits* out, const KwVFlat* vf, tsgpu_id_lists** ids_out);
 inline size_t group_kw_record_words(uint32_t k, uint32_t words) { return (size_t)k * words + 3; }
 int group_pack_keyword(tsgpu_ctx* ctx, const tsgpu_hits* local_dev, uint32_t n_q, uint32_t k, uint32_t words, uint64_t* block, hipStream_t s);

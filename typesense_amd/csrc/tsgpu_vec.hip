@@ -7,6 +7,7 @@
 #include <atomic>
 #include <thread>
 #include <tuple>
+#include <map>
 #include "tsgpu_host.h"
 #include <chrono>
 #include "vec_kernels.hip.h"
@@ -1805,6 +1806,38 @@ static int vector_search_flat(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu
     return kw_vector_flat_search(ctx, qs.data(), n_q, out, &vf, ids_out);
 }
 
+// The k-cut branch's finishing of ONE query (src/index.cpp:3389, :3682-3732), shared by both vector-search entry points: the query's k-NN result
+// (dist / lab, n of them, closest first) in label order, the query document skipped, abs() for cosine, the threshold, the sort scores, the Topster;
+// written to slot q of out; the ids that went to the Topster are appended to ids_out (ascending). `hits` is scratch.
+static void finish_kcut_query(tsgpu_ctx* ctx, int metric, const tsgpu_vec_query* p, const float* dist, const uint64_t* lab, uint32_t n, uint32_t tsz, uint32_t q,
+                              tsgpu_hits* out, std::vector<uint32_t>* ids_out, std::vector<std::pair<uint64_t, float>>& hits) {
+    HostTopster topster(tsz);
+    hits.clear();
+    for (uint32_t i = 0; i < n; i++) hits.emplace_back(lab[i], dist[i]);
+    std::sort(hits.begin(), hits.end(), [](const auto& a, const auto& b) { return a.first < b.first; });   // :3389
+    uint64_t added = 0;
+    for (auto& h : hits) {
+        if (p->query_doc_given && h.first == p->query_seq_id) continue;                        // :3686
+        const float d = metric == TSGPU_METRIC_COSINE ? std::fabs(h.second) : h.second;       // :3699
+        if (d > p->distance_threshold) continue;                                               // :3702
+        HostKV kv;
+        int64_t msi = -1;
+        host_sort_scores(ctx, p->sort, p->n_sort, h.first, 0, d, kv.scores, msi);
+        kv.match_score_index = (int8_t)msi;
+        kv.key = h.first;
+        kv.vector_distance = d;
+        if (msi >= 0) kv.text_match_score = kv.scores[msi];
+        topster.add(&kv);
+        added++;
+        if (ids_out) ids_out->push_back((uint32_t)h.first);                                     // nearest_ids (ascending: label order), :3727-3732
+    }
+    topster.sort();
+    write_hits(topster, q, out);
+    if (out->num_matched) out->num_matched[q] = added;
+    out->status[q] = TSGPU_OK;
+    if (out->search_cutoff) out->search_cutoff[q] = 0;
+}
+
 static int vector_search_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* p, const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out,
                               tsgpu_id_lists** ids_out) {
     if (ids_out) *ids_out = nullptr;
@@ -1853,31 +1886,7 @@ static int vector_search_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu
         if (ids_out) { lists.reset(new tsgpu_id_lists); lists->begin.assign(1, 0); }
         std::vector<std::pair<uint64_t, float>> hits;
         for (uint32_t q = 0; q < n_q; q++) {
-            HostTopster topster(tsz);
-            hits.clear();
-            for (uint32_t i = 0; i < kh.cnt[q]; i++) hits.emplace_back(kh.lab[(size_t)q * k + i], kh.dist[(size_t)q * k + i]);
-            std::sort(hits.begin(), hits.end(), [](const auto& a, const auto& b) { return a.first < b.first; });   // :3389
-            uint64_t added = 0;
-            for (auto& h : hits) {
-                if (p->query_doc_given && h.first == p->query_seq_id) continue;                        // :3686
-                const float d = f->metric == TSGPU_METRIC_COSINE ? std::fabs(h.second) : h.second;   // :3699
-                if (d > p->distance_threshold) continue;                                               // :3702
-                HostKV kv;
-                int64_t msi = -1;
-                host_sort_scores(ctx, p->sort, p->n_sort, h.first, 0, d, kv.scores, msi);
-                kv.match_score_index = (int8_t)msi;
-                kv.key = h.first;
-                kv.vector_distance = d;
-                if (msi >= 0) kv.text_match_score = kv.scores[msi];
-                topster.add(&kv);
-                added++;
-                if (lists) lists->ids.push_back((uint32_t)h.first);                                     // nearest_ids (ascending: label order), :3727-3732
-            }
-            topster.sort();
-            write_hits(topster, q, out);
-            if (out->num_matched) out->num_matched[q] = added;
-            out->status[q] = TSGPU_OK;
-            if (out->search_cutoff) out->search_cutoff[q] = 0;
+            finish_kcut_query(ctx, f->metric, p, kh.dist.data() + (size_t)q * k, kh.lab.data() + (size_t)q * k, kh.cnt[q], tsz, q, out, lists ? &lists->ids : nullptr, hits);
             if (lists) lists->begin.push_back(lists->ids.size());
         }
         if (ids_out) *ids_out = lists.release();
@@ -1892,6 +1901,256 @@ int tsgpu_vector_search_batch_ids(tsgpu_ctx* ctx, uint32_t vec_field_id, const t
                                   tsgpu_id_lists** ids_out) {
     if (!ids_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch_ids: ids_out is NULL");
     return vector_search_impl(ctx, vec_field_id, p, Q, mem_q, n_q, out, ids_out);
+}
+
+// ---- ONE PARAMETER BLOCK PER QUERY (tsgpu_vector_search_batch_per_query): the server's calling convention, every request with its own filter_by ----
+// host result arrays of a sub-batch in the caller's layout (the arrays the caller asked for), scattered back slot by slot
+struct PqHits {
+    std::vector<uint64_t> keys, num_matched; std::vector<int64_t> scores, text_match; std::vector<float> vector_distance; std::vector<int8_t> msi;
+    std::vector<uint32_t> n_hits; std::vector<int32_t> status, search_cutoff;
+    tsgpu_hits h{};
+    PqHits(const tsgpu_hits& like, uint32_t n) {
+        const size_t slots = (size_t)n * like.k_stride;
+        h.mem = TSGPU_MEM_HOST; h.k_stride = like.k_stride;
+        keys.resize(slots); h.keys = keys.data(); scores.resize(slots * 3); h.scores = scores.data();
+        n_hits.assign(n, 0); h.n_hits = n_hits.data(); status.assign(n, 0); h.status = status.data();
+        if (like.text_match) { text_match.resize(slots); h.text_match = text_match.data(); }
+        if (like.vector_distance) { vector_distance.resize(slots); h.vector_distance = vector_distance.data(); }
+        if (like.match_score_index) { msi.resize(slots); h.match_score_index = msi.data(); }
+        if (like.num_matched) { num_matched.assign(n, 0); h.num_matched = num_matched.data(); }
+        if (like.search_cutoff) { search_cutoff.assign(n, 0); h.search_cutoff = search_cutoff.data(); }
+    }
+    void scatter(uint32_t slot, uint32_t q, tsgpu_hits* out) const {
+        const size_t a = (size_t)slot * h.k_stride, b = (size_t)q * h.k_stride, n = std::min<size_t>(h.n_hits[slot], h.k_stride);
+        memcpy(out->keys + b, h.keys + a, n * 8); memcpy(out->scores + b * 3, h.scores + a * 3, n * 24);
+        if (h.text_match) memcpy(out->text_match + b, h.text_match + a, n * 8);
+        if (h.vector_distance) memcpy(out->vector_distance + b, h.vector_distance + a, n * 4);
+        if (h.match_score_index) memcpy(out->match_score_index + b, h.match_score_index + a, n);
+        out->n_hits[q] = h.n_hits[slot]; out->status[q] = h.status[slot];
+        if (h.num_matched) out->num_matched[q] = h.num_matched[slot];
+        if (h.search_cutoff) out->search_cutoff[q] = h.search_cutoff[slot];
+    }
+};
+static uint32_t flat_topster_size(const tsgpu_vec_query& p) {     // :3506-3512
+    return p.topster_size ? p.topster_size : std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(p.fetch_size, TSGPU_DEFAULT_TOPSTER_SIZE), p.n_filter));
+}
+
+// The FLAT queries of the batch, fq = their caller indices. Distinct lists (pointer, length) are translated to rows and uploaded once; slot s of the
+// sub-batch = the s-th flat query in list order (queries of one list adjacent: the ranking uploads the ids once for them), slot_q[s] = its caller index.
+// One ragged distance array, filled by one launch of vec_flat_ragged_distances_kernel per group of consecutive slots whose segments fit
+// "vec_flat_group_max_bytes" (1 GiB: what one launch's tile table and output window cover; the array itself is whole, the ONE ranking call reads all of
+// it), then kw_vector_flat_search ranks every slot's segment with its own threshold, list and Topster size. Lock and buffers as vector_search_flat.
+static int vector_search_pq_flat(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const std::vector<uint32_t>& fq, const float* Qh, uint32_t dim,
+                                 PqHits& res, std::vector<uint32_t>& slot_q, tsgpu_id_lists** lists_out) {
+    const uint32_t n = (uint32_t)fq.size();
+    std::map<std::pair<const uint32_t*, uint32_t>, uint32_t> list_of;
+    std::vector<const tsgpu_vec_query*> list_owner;
+    std::vector<uint32_t> lq(n), ord(n);
+    for (uint32_t j = 0; j < n; j++) {
+        const tsgpu_vec_query& p = params[fq[j]];
+        const auto it = list_of.emplace(std::make_pair(p.filter_ids, p.n_filter), (uint32_t)list_owner.size());
+        if (it.second) list_owner.push_back(&p);
+        lq[j] = it.first->second;
+        ord[j] = j;
+    }
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return lq[a] < lq[b]; });
+    const uint32_t n_lists = (uint32_t)list_owner.size();
+    std::vector<uint64_t> list_off(n_lists + 1, 0);
+    for (uint32_t l = 0; l < n_lists; l++) list_off[l + 1] = list_off[l] + list_owner[l]->n_filter;
+    // per slot: its query, its segment, the position of its query document; the tiles, group by group
+    slot_q.resize(n);
+    std::vector<VecFlatQuery> qa(n);
+    std::vector<uint64_t> off(n);
+    std::vector<float> thr(n), Qf((size_t)n * dim);
+    std::vector<VecFlatTile> tiles;
+    std::vector<size_t> group_tile0(1, 0);             // first tile of every group (+ the end)
+    uint64_t total = 0, group_bytes = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        const uint32_t qi = fq[ord[s]];
+        const tsgpu_vec_query& p = params[qi];
+        slot_q[s] = qi;
+        memcpy(Qf.data() + (size_t)s * dim, Qh + (size_t)qi * dim, (size_t)dim * 4);
+        uint32_t skip = VEC_FLAT_NO_SKIP;
+        if (p.query_doc_given) {                         // the query document itself is left out (:3686): its position in the list, if it is a member
+            const uint32_t* at = std::lower_bound(p.filter_ids, p.filter_ids + p.n_filter, p.query_seq_id);
+            if (at != p.filter_ids + p.n_filter && *at == p.query_seq_id) skip = (uint32_t)(at - p.filter_ids);
+        }
+        qa[s] = VecFlatQuery{list_off[lq[ord[s]]], total, skip, 0};
+        off[s] = total; thr[s] = p.distance_threshold;
+        const uint64_t bytes = 4ull * p.n_filter;
+        if (group_bytes && group_bytes + bytes > ctx->vec_flat_group_max_bytes) { group_tile0.push_back(tiles.size()); group_bytes = 0; }
+        group_bytes += bytes;
+        for (uint32_t first = 0; first < p.n_filter; first += VEC_FLAT_TILE) tiles.push_back(VecFlatTile{s, first, std::min<uint32_t>(VEC_FLAT_TILE, p.n_filter - first)});
+        total += p.n_filter;
+    }
+    group_tile0.push_back(tiles.size());
+    DevBuf d_dist, d_rows, d_q, d_qa, d_tiles;         // per call (another flat search may run while this one ranks): parked, not freed, on exit
+    struct Park { DevBuf* b[5]; ~Park() { for (DevBuf* x : b) if (x->p) { deferred_frees().park(x->p, x->cap, false); x->p = nullptr; x->cap = 0; } } } park{{&d_dist, &d_rows, &d_q, &d_qa, &d_tiles}};
+    bool cosine = false;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        VecField* f = get_field(ctx, vec_field_id);
+        if (!f || f->dim != dim) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_vector_search_batch_per_query: unknown vector field");
+        cosine = f->metric == TSGPU_METRIC_COSINE;
+        hipStream_t s = ctx->stream;
+        std::vector<uint32_t> rows(list_off[n_lists]);
+        for (uint32_t l = 0; l < n_lists; l++) {         // getDataByLabel throws for an unknown / deleted label: "likely not found", the id is skipped (:3355-3360)
+            const uint32_t* ids = list_owner[l]->filter_ids;
+            uint32_t* dst = rows.data() + list_off[l];
+            for (uint32_t i = 0; i < list_owner[l]->n_filter; i++) { uint32_t r; dst[i] = (f->find_row(ids[i], r) && f->h_ok[r]) ? r : 0xFFFFFFFFu; }
+        }
+        int rc;
+        if ((rc = d_dist.reserve(std::max<size_t>(total * 4, 16))) || (rc = d_rows.reserve(rows.size() * 4)) || (rc = d_q.reserve(Qf.size() * 4)) ||
+            (rc = d_qa.reserve(qa.size() * sizeof(VecFlatQuery))) || (rc = d_tiles.reserve(tiles.size() * sizeof(VecFlatTile)))) return rc;
+        if (f->n_rows == 0) TSGPU_HIP_TRY(hipMemsetAsync(d_dist.p, 0xFF, total * 4, s));      // (no row to read: every id is "not found", NaN)
+        else {
+            TSGPU_HIP_TRY(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(d_q.p, Qf.data(), Qf.size() * 4, hipMemcpyHostToDevice, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(d_qa.p, qa.data(), qa.size() * sizeof(VecFlatQuery), hipMemcpyHostToDevice, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(VecFlatTile), hipMemcpyHostToDevice, s));
+            if (cosine) hipLaunchKernelGGL(vec_normalize_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_q.as<float>(), n, dim);     // (:3362-3364)
+            for (size_t g = 0; g + 1 < group_tile0.size(); g++) {
+                const size_t t0 = group_tile0[g], nt = group_tile0[g + 1] - t0;
+                hipLaunchKernelGGL(vec_flat_ragged_distances_kernel, dim3((uint32_t)nt), dim3(VEC_THREADS), 0, s, (const float*)f->X.as<float>(), (const float*)d_q.as<float>(), dim,
+                                   (const uint32_t*)d_rows.as<uint32_t>(), (const VecFlatQuery*)d_qa.as<VecFlatQuery>(), (const VecFlatTile*)d_tiles.as<VecFlatTile>() + t0,
+                                   d_dist.as<float>(), ctx->vec_ip_lanes);
+                ctx->vec_search_pq_flat_launches.fetch_add(1);
+            }
+            TSGPU_HIP_TRY(hipGetLastError());
+        }
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));         // the ranking runs on a keyword lane's stream (and the host arrays above go out of scope)
+    }
+    ctx->vec_search_pq_flat_lists.fetch_add(n_lists);
+    ctx->vec_search_pq_flat_queries.fetch_add(n);
+    std::vector<tsgpu_kw_query> qs(n);
+    memset(qs.data(), 0, qs.size() * sizeof(tsgpu_kw_query));
+    for (uint32_t s = 0; s < n; s++) {
+        const tsgpu_vec_query& p = params[slot_q[s]];
+        tsgpu_kw_query& q = qs[s];
+        q.n_sort = p.n_sort;
+        for (uint32_t j = 0; j < p.n_sort; j++) q.sort[j] = p.sort[j];
+        q.topster_size = flat_topster_size(p);
+        q.filter_ids = p.filter_ids; q.n_filter = p.n_filter;
+    }
+    KwVFlat vf{d_dist.as<float>(), 0, 0.0f, cosine, off.data(), thr.data()};
+    return kw_vector_flat_search(ctx, qs.data(), n, &res.h, &vf, lists_out);
+}
+
+static int vector_search_pq_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out,
+                                 tsgpu_id_lists** ids_out) {
+    static const char* who = "tsgpu_vector_search_batch_per_query";
+    if (ids_out) *ids_out = nullptr;
+    if (!ctx || !out || (n_q != 0 && (!params || !Q))) return fail(TSGPU_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (n_q == 0) { if (ids_out) { *ids_out = new (std::nothrow) tsgpu_id_lists; if (*ids_out) (*ids_out)->begin.assign(1, 0); } return ok(); }
+    if (!out->keys || !out->scores || !out->n_hits || !out->status) return fail(TSGPU_ERR_INVALID, std::string(who) + ": missing output arrays");
+    if (out->mem != TSGPU_MEM_HOST) return fail(TSGPU_ERR_UNSUPPORTED, std::string(who) + ": host outputs only");
+    try {
+        uint32_t num_docs, dim; uint64_t n_rows; int metric;
+        std::vector<float> Qcopy;
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            VecField* f = get_field(ctx, vec_field_id);
+            if (!f) return fail(TSGPU_ERR_NOT_FOUND, std::string(who) + ": unknown vector field");
+            num_docs = ctx->num_docs; dim = f->dim; n_rows = f->n_rows; metric = f->metric;
+            if (mem_q == TSGPU_MEM_DEVICE) {             // the branches gather their own queries on the host
+                (void)hipSetDevice(ctx->device);
+                Qcopy.resize((size_t)n_q * dim);
+                TSGPU_HIP_TRY(hipMemcpyAsync(Qcopy.data(), Q, Qcopy.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+                TSGPU_HIP_TRY(hipStreamSynchronize(ctx->stream));
+            }
+        }
+        const float* Qh = mem_q == TSGPU_MEM_DEVICE ? Qcopy.data() : Q;
+        // ---- classify: what tsgpu_vector_search_batch refuses as a call for reasons in the parameter block is the query's status here ----
+        std::vector<uint32_t> fq, kq, k_of(n_q, 0), tsz_of(n_q, 0);
+        for (uint32_t i = 0; i < n_q; i++) {
+            const tsgpu_vec_query& p = params[i];
+            int st = TSGPU_OK;
+            bool flat = false;
+            if (p.n_sort > 3) st = TSGPU_ERR_INVALID;
+            else if ((p.n_filter && !p.filter_ids) || (p.n_excluded && !p.excluded_ids)) st = TSGPU_ERR_INVALID;
+            else {
+                for (uint32_t j = 0; j < p.n_sort; j++) if (p.sort[j].kind >= TSGPU_SORT_EVAL) st = TSGPU_ERR_UNSUPPORTED;
+                flat = (p.filter_by_provided || p.n_filter) && p.n_filter != 0 && (uint64_t)p.n_filter < p.flat_search_cutoff;     // :3664
+            }
+            if (st == TSGPU_OK && flat) {
+                const uint32_t tsz = flat_topster_size(p);
+                if (tsz <= TSGPU_MAX_TOPK && out->k_stride < tsz) st = TSGPU_ERR_INVALID;      // (a larger Topster is the ranking's own per-query 501)
+            } else if (st == TSGPU_OK) {
+                uint32_t k = p.k == 0 ? p.fetch_size : p.k;                                    // :3646
+                if (k == 0) st = TSGPU_ERR_INVALID;
+                else {
+                    const bool doc_passes = p.query_doc_given && !(p.n_excluded && std::binary_search(p.excluded_ids, p.excluded_ids + p.n_excluded, p.query_seq_id)) &&
+                                            (p.n_filter == 0 || std::binary_search(p.filter_ids, p.filter_ids + p.n_filter, p.query_seq_id));
+                    if (doc_passes) k++;                                                       // :3651-3654
+                    uint32_t tsz = p.topster_size ? p.topster_size : std::max<uint32_t>(p.fetch_size, TSGPU_DEFAULT_TOPSTER_SIZE);
+                    if (!p.topster_size) tsz = std::max<uint32_t>(1, std::min<uint32_t>(tsz, p.n_filter ? p.n_filter : std::max<uint32_t>(num_docs, (uint32_t)n_rows)));   // :3506-3512
+                    if (k > TSGPU_MAX_TOPK) st = TSGPU_ERR_UNSUPPORTED;
+                    else if (out->k_stride < std::min<uint32_t>(tsz, k)) st = TSGPU_ERR_INVALID;
+                    k_of[i] = k; tsz_of[i] = tsz;
+                }
+            }
+            if (st != TSGPU_OK) {
+                out->status[i] = st; out->n_hits[i] = 0;
+                if (out->num_matched) out->num_matched[i] = 0;
+                if (out->search_cutoff) out->search_cutoff[i] = 0;
+            } else (flat ? fq : kq).push_back(i);
+        }
+        std::vector<std::vector<uint32_t>> ids_of(ids_out ? n_q : 0);
+        // ---- k-cut queries: ONE filtered exact k-NN at K = max k_i; query i keeps its first k_i results (the order (distance, label) is total and a
+        //      pair's distance does not depend on k: the k_i nearest are the prefix of the K nearest), then the finishing of the single call ----
+        if (!kq.empty()) {
+            const uint32_t nk = (uint32_t)kq.size();
+            uint32_t K = 0;
+            std::vector<float> Qk((size_t)nk * dim);
+            std::vector<tsgpu_vec_filter> fl(nk);
+            for (uint32_t j = 0; j < nk; j++) {
+                const tsgpu_vec_query& p = params[kq[j]];
+                K = std::max(K, k_of[kq[j]]);
+                memcpy(Qk.data() + (size_t)j * dim, Qh + (size_t)kq[j] * dim, (size_t)dim * 4);
+                fl[j] = tsgpu_vec_filter{p.n_filter ? 1u : 0u, p.n_filter, p.n_filter ? p.filter_ids : nullptr, p.n_excluded, p.n_excluded ? p.excluded_ids : nullptr};
+            }
+            KnnHost kh;
+            kh.dist.assign((size_t)nk * K, 0.f); kh.lab.assign((size_t)nk * K, 0); kh.cnt.assign(nk, 0);
+            if (const int rc = tsgpu_vec_knn_batch_filtered(ctx, vec_field_id, Qk.data(), TSGPU_MEM_HOST, nk, K, fl.data(), kh.dist.data(), kh.lab.data(), kh.cnt.data(), TSGPU_MEM_HOST)) return rc;
+            std::vector<std::pair<uint64_t, float>> hits;
+            for (uint32_t j = 0; j < nk; j++) {
+                const uint32_t i = kq[j];
+                finish_kcut_query(ctx, metric, &params[i], kh.dist.data() + (size_t)j * K, kh.lab.data() + (size_t)j * K, std::min(kh.cnt[j], k_of[i]), tsz_of[i], i, out,
+                                  ids_out ? &ids_of[i] : nullptr, hits);
+            }
+            ctx->vec_search_pq_kcut_queries.fetch_add(nk);
+        }
+        // ---- flat queries: one ragged distance array, one ranking call; scattered back into the caller's order ----
+        if (!fq.empty()) {
+            PqHits res(*out, (uint32_t)fq.size());
+            std::vector<uint32_t> slot_q;
+            tsgpu_id_lists* fl_lists = nullptr;
+            const int rc = vector_search_pq_flat(ctx, vec_field_id, params, fq, Qh, dim, res, slot_q, ids_out ? &fl_lists : nullptr);
+            std::unique_ptr<tsgpu_id_lists> hold(fl_lists);
+            if (rc) return rc;
+            for (uint32_t s = 0; s < (uint32_t)slot_q.size(); s++) {
+                res.scatter(s, slot_q[s], out);
+                if (ids_out) ids_of[slot_q[s]].assign(hold->ids.begin() + hold->begin[s], hold->ids.begin() + hold->begin[s + 1]);
+            }
+        }
+        if (ids_out) {
+            std::unique_ptr<tsgpu_id_lists> lists(new tsgpu_id_lists);
+            lists->begin.assign(1, 0);
+            for (uint32_t i = 0; i < n_q; i++) { lists->ids.insert(lists->ids.end(), ids_of[i].begin(), ids_of[i].end()); lists->begin.push_back(lists->ids.size()); }
+            *ids_out = lists.release();
+        }
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, std::string(who) + ": host allocation failed"); }
+    return ok();
+}
+
+int tsgpu_vector_search_batch_per_query(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out) {
+    return vector_search_pq_impl(ctx, vec_field_id, params, Q, mem_q, n_q, out, nullptr);
+}
+int tsgpu_vector_search_batch_per_query_ids(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out,
+                                            tsgpu_id_lists** ids_out) {
+    if (!ids_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch_per_query_ids: ids_out is NULL");
+    return vector_search_pq_impl(ctx, vec_field_id, params, Q, mem_q, n_q, out, ids_out);
 }
 
 // reciprocal rank fusion of ONE query, exactly src/index.cpp:4094-4211: `kw` = the keyword Topster content in sort()

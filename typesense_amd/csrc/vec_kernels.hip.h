@@ -62,8 +62,8 @@ __device__ inline float ord_f32(uint32_t o) {
 // A lane's 16 accumulator rows of one (rb, cb) block are rows g0 + 4 * (lane >> 5) + (el & 3) + 8 * (el >> 2) of the 32-aligned group
 // g0 = r0 + 64 * strip + 32 * rb: ONE word load per (rb, cb) and lane decides all of them.
 // vec_hnsw_search_kernel's PQ instantiations (tsgpu_vec_hnsw_search_batch_filtered) read the same maps, one bit per admission test.
-// Out of scope here: a per-query parameter block for tsgpu_vector_search_batch, the tsgpu_group_* shard forms (they keep their
-// per-query loop), filters that already live on the device.
+// tsgpu_vector_search_batch_per_query's k-cut queries come through the same batch (its flat queries: vec_flat_ragged_distances_kernel below).
+// Out of scope here: the tsgpu_group_* shard forms (they keep their per-query loop), filters that already live on the device.
 static const uint32_t VEC_QMASK_NONE = 0xFFFFFFFFu;
 struct VecQMasks {
     const uint32_t* bits;      // [n_maps][words]
@@ -1211,6 +1211,56 @@ __global__ __launch_bounds__(VEC_THREADS) void vec_rescore_kernel(const float* _
         const uint32_t row = surv[ic];
         const float d = ip_distance_group16(qs, X + (size_t)row * dim, dim, sub, ip_lanes);
         if (i < n && sub == 0) keys[i] = ((uint64_t)f32_ord(d) << 32) | row;
+    }
+}
+
+// The FLAT branch for a batch whose queries each own a filter list (tsgpu_vector_search_batch_per_query): ONE launch computes every query's distances
+// to the rows of ITS list into one ragged array. The grid runs over a host-built tile table; a tile = (query, first item, item count <= VEC_FLAT_TILE) is
+// block-uniform and never empty. Per query: where its list's rows start (distinct lists are uploaded once; queries that pass the same list share the
+// rows), where its segment of `out` starts (aligned with the list), and `skip` = the one position that holds the query's own document
+// (`vec:([], id: X)`, src/index.cpp:3686; VEC_FLAT_NO_SKIP = none) — an argument of the query, not an edit of the shared rows. out = NaN for that
+// position and for rows[i] == 0xFFFFFFFF (no vector / deleted). The workgroup stages its query in LDS (dim <= VEC_RESCORE_LDS_DIM) and walks its tile
+// like vec_rescore_kernel: four lanes per row where dim % 16 == 0 (ip_dot16_quad, 64 rows per trip), else 16 lanes per row (ip_distance_group16) —
+// the bits of vec_flat_distances_kernel, tsgpu_vec_distances and the k-NN paths. Idle lanes recompute the tile's last row (uniform shuffles).
+// VEC_FLAT_TILE = 256 items: one trip of the quad form fills the four wavefronts (64 rows), a tile is four such trips, so staging the query costs
+// 1/256 of the tile's row traffic; 16 KiB of LDS per workgroup leaves ten workgroups per CU (160 KiB), more than the 8 the 256-thread blocks fill.
+static const uint32_t VEC_FLAT_TILE = 256;
+static const uint32_t VEC_FLAT_NO_SKIP = 0xFFFFFFFFu;
+struct VecFlatTile { uint32_t q, first, count; };
+struct VecFlatQuery { uint64_t rows_off, out_off; uint32_t skip, pad; };
+__global__ __launch_bounds__(VEC_THREADS) void vec_flat_ragged_distances_kernel(const float* __restrict__ X, const float* __restrict__ Q, uint32_t dim,
+                                                                                 const uint32_t* __restrict__ rows, const VecFlatQuery* __restrict__ qargs,
+                                                                                 const VecFlatTile* __restrict__ tiles, float* __restrict__ out, uint32_t ip_lanes) {
+    __shared__ __attribute__((aligned(16))) float qs_lds[VEC_RESCORE_LDS_DIM];
+    const uint32_t t = threadIdx.x;
+    const VecFlatTile tl = tiles[blockIdx.x];
+    const VecFlatQuery qa = qargs[tl.q];
+    const float* qs = Q + (size_t)tl.q * dim;
+    if (dim <= VEC_RESCORE_LDS_DIM) {
+        for (uint32_t i = t; i < dim; i += VEC_THREADS) qs_lds[i] = qs[i];
+        __syncthreads();
+        qs = qs_lds;
+    }
+    const uint32_t* __restrict__ r = rows + qa.rows_off + tl.first;
+    float* __restrict__ o = out + qa.out_off + tl.first;
+    const uint32_t n = tl.count;
+    const uint32_t skip = (qa.skip != VEC_FLAT_NO_SKIP && qa.skip >= tl.first) ? qa.skip - tl.first : VEC_FLAT_NO_SKIP;     // position inside the tile
+    const float nan = __uint_as_float(0x7FC00000u);
+    if (dim % 16 == 0) {
+        for (uint32_t i0 = 0; i0 < n; i0 += VEC_THREADS / 4) {
+            const uint32_t i = i0 + (t >> 2);
+            const uint32_t row = r[i < n ? i : n - 1];
+            const float d = ip_add(1.0f, -ip_dot16_quad<24>(qs, X + (size_t)(row != 0xFFFFFFFFu ? row : 0) * dim, dim, t & 3, ip_lanes));
+            if (i < n && (t & 3) == 0) o[i] = (row == 0xFFFFFFFFu || i == skip) ? nan : d;
+        }
+        return;
+    }
+    const uint32_t sub = t & 15, grp = t >> 4;
+    for (uint32_t i0 = 0; i0 < n; i0 += VEC_THREADS / 16) {
+        const uint32_t i = i0 + grp;
+        const uint32_t row = r[i < n ? i : n - 1];
+        const float d = ip_distance_group16(qs, X + (size_t)(row != 0xFFFFFFFFu ? row : 0) * dim, dim, sub, ip_lanes);
+        if (i < n && sub == 0) o[i] = (row == 0xFFFFFFFFu || i == skip) ? nan : d;
     }
 }
 

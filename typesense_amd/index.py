@@ -660,7 +660,29 @@ class GpuIndex:
         `vec:([], id: X)` (Q = X's stored vector). want_ids: also return all_result_ids per query -> (hits, [ids])."""
         Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
         p = B.VecQueryC()
-        p.k, p.fetch_size, p.distance_threshold, p.n_sort, p.topster_size = k, fetch_size, distance_threshold, len(sort), topster_size
+        keep = self._fill_vec_query(p, k, fetch_size, distance_threshold, sort, topster_size, filter_ids, excluded_ids, flat_search_cutoff, query_doc)
+        hits = Hits(Q.shape[0], k_stride)
+        hs = hits.c_struct()
+        if not want_ids:
+            self._ck(self.L.tsgpu_vector_search_batch(self.h, field_id, C.byref(p), _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs)))
+            return hits
+        lists = C.c_void_p()
+        self._ck(self.L.tsgpu_vector_search_batch_ids(self.h, field_id, C.byref(p), _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs), C.byref(lists)))
+        try:
+            ids = []
+            for q in range(Q.shape[0]):
+                cnt = self.L.tsgpu_id_lists_count(lists, q)
+                ids.append(np.ctypeslib.as_array(self.L.tsgpu_id_lists_ids(lists, q), shape=(cnt,)).copy() if cnt else np.zeros(0, np.uint32))
+        finally:
+            self.L.tsgpu_id_lists_free(lists)
+        return hits, ids
+
+    @staticmethod
+    def _fill_vec_query(p, k=0, fetch_size=10, distance_threshold=B.FLT_MAX, sort=((B.SORT_VECTOR_DISTANCE, -1, 0), (B.SORT_SEQ_ID, 1, 0)), topster_size=0,
+                        filter_ids=None, excluded_ids=None, flat_search_cutoff=0, query_doc=None, n_sort=None):
+        """one tsgpu_vec_query from vector_search_batch's keyword arguments; returns the id arrays the block points into (keep them alive for the call).
+        n_sort: the count sent down when it is not len(sort) (tests of the refusals)"""
+        p.k, p.fetch_size, p.distance_threshold, p.n_sort, p.topster_size = k, fetch_size, distance_threshold, len(sort) if n_sort is None else n_sort, topster_size
         for i, s in enumerate(sort):
             p.sort[i].kind, p.sort[i].order, p.sort[i].column = s
         f = _u32(filter_ids) if filter_ids is not None else None
@@ -670,13 +692,34 @@ class GpuIndex:
         p.excluded_ids, p.n_excluded = (e.ctypes.data if e is not None and e.size else None), (e.size if e is not None else 0)
         p.flat_search_cutoff = int(flat_search_cutoff)
         p.query_doc_given, p.query_seq_id = (1, int(query_doc)) if query_doc is not None else (0, 0)
+        return f, e
+
+    def vector_search_batch_per_query(self, field_id, Q, params, k_stride=250, want_ids=False):
+        """tsgpu_vector_search_batch_per_query: params[i] = a dict of vector_search_batch's keyword arguments (k, fetch_size, distance_threshold, sort,
+        topster_size, filter_ids, excluded_ids, flat_search_cutoff, query_doc) for Q[i]. A refused query has its code in hits.status[i] and no hits; the
+        call raises only for what concerns the whole call. Queries that pass the SAME array object as filter_ids share one upload of it.
+        want_ids: also return all_result_ids per query -> (hits, [ids])."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
+        if len(params) != Q.shape[0]:
+            raise ValueError("one parameter block per query: %d blocks for %d queries" % (len(params), Q.shape[0]))
+        arr = (B.VecQueryC * max(len(params), 1))()
+        keep, converted = [], {}                      # every id array stays alive until the call returns; one conversion per array object
+        for i, d in enumerate(params):
+            d = dict(d)
+            for name in ("filter_ids", "excluded_ids"):
+                a = d.get(name)
+                if a is not None:
+                    if id(a) not in converted:
+                        converted[id(a)] = (a, _u32(a))
+                    d[name] = converted[id(a)][1]
+            keep.append(self._fill_vec_query(arr[i], **d))
         hits = Hits(Q.shape[0], k_stride)
         hs = hits.c_struct()
         if not want_ids:
-            self._ck(self.L.tsgpu_vector_search_batch(self.h, field_id, C.byref(p), _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs)))
+            self._ck(self.L.tsgpu_vector_search_batch_per_query(self.h, field_id, arr, _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs)))
             return hits
         lists = C.c_void_p()
-        self._ck(self.L.tsgpu_vector_search_batch_ids(self.h, field_id, C.byref(p), _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs), C.byref(lists)))
+        self._ck(self.L.tsgpu_vector_search_batch_per_query_ids(self.h, field_id, arr, _vp(Q), B.MEM_HOST, Q.shape[0], C.byref(hs), C.byref(lists)))
         try:
             ids = []
             for q in range(Q.shape[0]):
