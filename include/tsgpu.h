@@ -394,6 +394,66 @@ void tsgpu_id_lists_free(tsgpu_id_lists* lists);
 int tsgpu_keep_result_ids(tsgpu_ctx* ctx, int keep);
 uint64_t tsgpu_result_ids(tsgpu_ctx* ctx, uint32_t q, uint32_t* out_host, uint64_t cap);
 
+/* ------------------------------------------------------------------ infix search (Index::search_infix, src/index.cpp:3265-3343; Index::do_infix_search, :6144-6272) */
+/* The VOCABULARY MIRROR of a query_by field declared `infix: true` (Index::infix_index: the field's tokens, src/index.cpp:852-856): token bytes + the
+ * term id the posting lists of the same field are fed under. Part of the snapshot: every call below is STAGED and becomes visible at the next
+ * tsgpu_commit(); a search keeps the vocabulary it started on. A commit uploads the appended tokens and 4 bytes per erased / replaced one; the whole
+ * vocabulary only after tsgpu_infix_tokens_load, when the device arrays are full, and when the dead slots outnumber the live ones (and reach option
+ * "infix_compact_min_slots", default 1024; counter "infix_compactions"; "infix_commit_uploaded_bytes" = what the last commit uploaded for all fields).
+ * Tokens have >= 1 byte and may hold any byte value (compared as unsigned bytes, no case folding: the reference's tokens are normalised already); a
+ * term id is unique within a field. A field's vocabulary is at most 4 GiB - 16 bytes (501 beyond). */
+#define TSGPU_MAX_INFIX_PATTERN 255     /* bytes; a longer pattern -> 501 for that query */
+/* declares field_id (it must exist: 404) an infix field with an empty vocabulary; idempotent (schema add, src/index.cpp:7665-7672) */
+int tsgpu_infix_enable(tsgpu_ctx* ctx, uint32_t field_id);
+/* REPLACES the field's vocabulary: token i = bytes[byte_ptr[i] .. byte_ptr[i + 1]) under term_ids[i] (bulk load; n_tokens = 0: schema drop, :7733-7740) */
+int tsgpu_infix_tokens_load(tsgpu_ctx* ctx, uint32_t field_id, uint32_t n_tokens, const uint32_t* term_ids, const uint64_t* byte_ptr, const uint8_t* bytes);
+/* infix_index.at(field)[shard]->insert(token), src/index.cpp:852-856; an existing term_id gets the new bytes */
+int tsgpu_infix_token_upsert(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, const uint8_t* bytes, uint32_t len);
+/* infix_sets[shard]->erase(token), src/index.cpp:7352-7356; erasing a term_id the field does not hold is not an error */
+int tsgpu_infix_token_erase(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id);
+/* live tokens of the field in the COMMITTED snapshot (0: not an infix field) */
+uint64_t tsgpu_infix_num_tokens(tsgpu_ctx* ctx, uint32_t field_id);
+
+/* One (field, query) of do_infix_search's field loop. Token test (:3305-3307): p = token.find(pattern), the FIRST occurrence only; the token matches iff
+ * p != npos && p <= max_extra_prefix && token.size() - (p + pattern.size()) <= max_extra_suffix (the API defaults of both limits: INT16_MAX). */
+typedef struct tsgpu_infix_query {
+    uint32_t field_id;
+    const uint8_t* pattern;                          /* host; query_tokens[0].value */
+    uint32_t pattern_len;                            /* 0 behaves like std::string::find(""): position 0 of every token */
+    uint32_t max_extra_prefix, max_extra_suffix;
+    uint32_t n_sort;
+    tsgpu_sort_by sort[TSGPU_MAX_SORT_KEYS];
+    uint32_t topster_size;                           /* as tsgpu_kw_query::topster_size */
+    const uint32_t* excluded_ids;                    /* curated_ids_sorted (:6190-6197): ascending, host; may be NULL */
+    uint32_t n_excluded;
+    const uint32_t* filter_ids;                      /* ascending, host; NULL = no filter; non-NULL with n_filter == 0 = a filter that matched nothing (:6199-6208) */
+    uint32_t n_filter;
+    uint64_t deadline_us;                            /* absolute epoch us; a query already late when the batch is planned reports 408 and search_cutoff = 1 */
+} tsgpu_infix_query;
+
+/* Infix search of a batch of (field, pattern) queries, all on the device. Per field ONE pass over its vocabulary serves every query of the batch that names it
+ * (infix_scan_kernel: counters "infix_scan_launches", "infix_tokens_scanned", "infix_tokens_matched"); the posting lists of the matching tokens that have one
+ * (:3308-3313) are united as one bit per seq_id straight from the packed lists ("infix_lists_marked"); excluded ids are cleared, the filter's bitmap is ANDed
+ * (:6190-6208), and the surviving ids — an ascending DEVICE list — are ranked by the wildcard kernels exactly as tsgpu_wildcard_search_batch ranks the same
+ * list given as filter_ids: text_match 100 where _text_match is a sort key (compute_sort_scores(..., 100, ...), :6219-6229), vector_distance -1 unless a
+ * _vector_query key sets it, num_matched = ids ranked, the top topster_size in Topster::sort() order, every sort kind that entry point serves.
+ *   n_tokens_matched[q] (nullable): tokens of the vocabulary that pass the token test (with or without a posting list);
+ *   n_infix_ids[q] (nullable): size of the union BEFORE exclusion and filter. Non-zero: the reference pushes onto searched_queries (:6266); zero: no hits and
+ *     nothing else (:6183) — never "a wildcard without a filter";
+ *   *ids_out (nullable): per query the surviving ids, ascending (what the caller ORs into all_result_ids, :6256-6260); a per-call object, tsgpu_id_lists_free.
+ * Per-query status: 400 a field that is not an infix field of the snapshot, bad arguments; 501 pattern_len > TSGPU_MAX_INFIX_PATTERN, a sort slot the
+ * wildcard entry point refuses; 408 already late at planning. The call answers 501 for out->mem != TSGPU_MEM_HOST and on a doc-range shard. There is no
+ * deadline INSIDE the front: every pass is bounded (one read of the vocabulary, one of the matched lists, one of the bitmaps); the ranking checks it as the
+ * wildcard search does. Scratch (bitmaps: num_docs / 8 bytes per query, twice that with a filter, plus the id lists) is bounded by option
+ * "infix_round_max_bytes" (default 2 GiB): a batch that needs more runs in rounds (counter "infix_rounds"). "infix_tile_tokens" / "infix_tile_bytes" (counters):
+ * the scan kernel's tile. Safe with concurrent callers (one infix batch at a time per context, its ranking included: the id lists are the front's scratch);
+ * 1-query calls are not coalesced. MEASUREMENT ONLY: option "infix_timing" = 1 puts a stream sync behind every phase and adds its host wall clock to the counters
+ * "infix_scan_us" (scan launches incl. the match lists' way back), "infix_mark_us", "infix_expand_us" (exclusion, filter, count, expansion), "infix_rank_us".
+ * TESTS ONLY: option "infix_test_hold_snapshot" = 1: infix batches run on the snapshot published at that moment until 0 lets it go (what a search that
+ * started before later commits sees). */
+int tsgpu_infix_search_batch(tsgpu_ctx* ctx, const tsgpu_infix_query* queries, uint32_t n_queries, tsgpu_hits* out,
+                             uint32_t* n_tokens_matched, uint64_t* n_infix_ids, tsgpu_id_lists** ids_out);
+
 /* ------------------------------------------------------------------ group_by: the DISTINCT Topster */
 /* One pass of the reference's two-pass grouped search (Index::run_search, src/index.cpp:2488-2760) through search_across_fields with
  * group_limit != 0 (src/index.cpp:5511-5520, 5546-5549) — or Index::search_wildcard's grouped loop (:6736-6760) — into

@@ -15,6 +15,7 @@ METRIC_IP, METRIC_COSINE = 0, 1
 MAX_SCORE, MAX_WEIGHT, SUM_SCORE = 0, 1, 2
 MAX_QUERY_TOKENS = 10
 LIST_HAS_BREAKS = 1
+MAX_INFIX_PATTERN = 255
 FLT_MAX = 3.4028234663852886e38
 
 
@@ -38,6 +39,14 @@ class KwQueryC(C.Structure):
                 ("filter_ids", C.POINTER(C.c_uint32)), ("n_filter", C.c_uint32),
                 ("deadline_us", C.c_uint64), ("n_dropped", C.c_uint32), ("dropped_term_ids", C.c_uint32 * 4),
                 ("is_synonym_query", C.c_uint8), ("demote_synonym_match", C.c_uint8), ("syn_orig_num_tokens_p1", C.c_uint8), ("orig_num_tokens", C.c_uint8)]
+
+
+class InfixQueryC(C.Structure):
+    _fields_ = [("field_id", C.c_uint32), ("pattern", C.c_void_p), ("pattern_len", C.c_uint32),
+                ("max_extra_prefix", C.c_uint32), ("max_extra_suffix", C.c_uint32),
+                ("n_sort", C.c_uint32), ("sort", SortBy * 3), ("topster_size", C.c_uint32),
+                ("excluded_ids", C.c_void_p), ("n_excluded", C.c_uint32),
+                ("filter_ids", C.c_void_p), ("n_filter", C.c_uint32), ("deadline_us", C.c_uint64)]
 
 
 class HitsC(C.Structure):
@@ -134,6 +143,7 @@ EXPORTS = [
     "tsgpu_abi_version", "tsgpu_create", "tsgpu_destroy", "tsgpu_last_error", "tsgpu_set_stream", "tsgpu_set_option", "tsgpu_get_counter", "tsgpu_device_bytes",
     "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_create_vector_query", "tsgpu_sort_key_destroy", "tsgpu_commit",
     "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_term_blocks_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
+    "tsgpu_infix_enable", "tsgpu_infix_tokens_load", "tsgpu_infix_token_upsert", "tsgpu_infix_token_erase", "tsgpu_infix_num_tokens", "tsgpu_infix_search_batch",
     "tsgpu_keyword_search_batch_ids", "tsgpu_keyword_search_grouped_batch", "tsgpu_keyword_search_grouped_candidates_batch", "tsgpu_id_lists_count", "tsgpu_id_lists_ids", "tsgpu_id_lists_free", "tsgpu_facet_set", "tsgpu_facet_count_batch", "tsgpu_facet_count_grouped_batch", "tsgpu_facet_range_count_batch", "tsgpu_facet_stats_batch", "tsgpu_facet_value_set", "tsgpu_facet_value_count_batch",
     "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch", "tsgpu_vec_knn_batch_filtered",
     "tsgpu_vec_hnsw_load", "tsgpu_vec_hnsw_enable", "tsgpu_vec_hnsw_build", "tsgpu_vec_hnsw_export", "tsgpu_vec_hnsw_search_batch", "tsgpu_vec_hnsw_search_batch_filtered", "tsgpu_vec_distances", "tsgpu_ip_distance", "tsgpu_vector_search_batch", "tsgpu_vector_search_batch_ids", "tsgpu_vector_search_batch_per_query", "tsgpu_vector_search_batch_per_query_ids", "tsgpu_hybrid_search_batch", "tsgpu_hybrid_fuse_batch", "tsgpu_keyword_aux_scores", "tsgpu_merge_shard_hits", "tsgpu_merge_shard_hits_device", "tsgpu_last_timings", "tsgpu_last_aux_timings", "tsgpu_kw_last_touched", "tsgpu_kw_lists_footprint",
@@ -200,6 +210,13 @@ def lib(path=None):
     L.tsgpu_keyword_search_batch_ids.argtypes = [vp, vp, u32, C.POINTER(HitsC), C.POINTER(vp)]
     L.tsgpu_keyword_search_grouped_batch.argtypes = [vp, vp, vp, u32, C.POINTER(HitsC), C.POINTER(GroupedHitsC), C.POINTER(vp)]
     L.tsgpu_keyword_search_grouped_candidates_batch.argtypes = [vp, vp, vp, vp, u32, C.POINTER(HitsC), C.POINTER(GroupedHitsC), vp, C.POINTER(vp)]
+    L.tsgpu_infix_enable.argtypes = [vp, u32]
+    L.tsgpu_infix_tokens_load.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.tsgpu_infix_token_upsert.argtypes = [vp, u32, u32, vp, u32]
+    L.tsgpu_infix_token_erase.argtypes = [vp, u32, u32]
+    L.tsgpu_infix_num_tokens.argtypes = [vp, u32]
+    L.tsgpu_infix_num_tokens.restype = u64
+    L.tsgpu_infix_search_batch.argtypes = [vp, vp, u32, C.POINTER(HitsC), vp, vp, C.POINTER(vp)]
     L.tsgpu_id_lists_count.argtypes = [vp, u32]
     L.tsgpu_id_lists_count.restype = u64
     L.tsgpu_id_lists_ids.argtypes = [vp, u32]

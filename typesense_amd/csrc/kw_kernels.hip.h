@@ -223,6 +223,8 @@ struct KwQueryDev {                  // one search_across_fields call
     uint8_t pad2[3];
     uint32_t wild_base;              // wildcard query without filter ids on a doc-range shard (context options doc_range_lo / _hi): the ids scanned are wild_base + [0, wild_n_ids)
     uint32_t pad3;
+    uint64_t wild_ids;               // wildcard query whose n_filt filter ids are ALREADY on the device (the id list the infix front expanded, kw_infix.hip.h): their
+                                     // address; 0 = the filter ids follow the excluded ids in the aux arena
 };
 
 // query_by over several fields (get_field_token_its, src/index.cpp:5598-5660): token t is the UNION over the fields of its
@@ -2368,7 +2370,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_wildcard_kernel(IndexView ix, c
     __syncthreads();
     const KwQueryDev& q = sq;
     const uint32_t* ex = aux_ids + q.aux_off;
-    const uint32_t* fl = ex + q.n_excl;
+    const uint32_t* fl = q.wild_ids ? (const uint32_t*)q.wild_ids : ex + q.n_excl;
     uint32_t* my_ids_out = ids_out ? ids_out + q.ids_out_off + wi.ids_out_off : nullptr;
     for (uint32_t b = wi.blk_begin; b < wi.blk_end; b++) {
         if (((b - wi.blk_begin) & 15) == 0 && kw_out_of_time(ix, q, wi.query, &s_stop)) break;
@@ -3357,13 +3359,16 @@ __global__ __launch_bounds__(KW_THREADS) void kw_ids_gather_kernel(const uint32_
     for (uint32_t i = threadIdx.x; i < sg.cnt; i += KW_THREADS) out[sg.dst + i] = ids[sg.src + i];
 }
 // ascending ids of one group's bitmap -> out[0 .. found) (one workgroup walks the words, 256 at a time, with a running base)
-__global__ __launch_bounds__(KW_THREADS) void kw_idset_expand_kernel(const uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ out, uint64_t cap) {
+// (the walk itself: words [w_begin, w_end) of the bitmap, the first id written to out[start]; every thread of a KW_THREADS workgroup calls it. The infix
+// front expands one bitmap with many workgroups, each on its own range behind the counts of the earlier ones: kw_infix.hip.h)
+__device__ inline void idset_expand_range(const uint32_t* __restrict__ bits, uint64_t w_begin, uint64_t w_end, uint32_t* __restrict__ out, uint64_t start, uint64_t cap) {
     __shared__ uint32_t s_wave[KW_THREADS / 64];
     __shared__ uint64_t s_base;
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) s_base = 0;
+    const uint64_t n_words = w_end;
+    if (t == 0) s_base = start;
     __syncthreads();
-    for (uint64_t w0 = 0; w0 < n_words; w0 += KW_THREADS) {
+    for (uint64_t w0 = w_begin; w0 < n_words; w0 += KW_THREADS) {
         const uint64_t w = w0 + t;
         uint32_t word = w < n_words ? bits[w] : 0u;
         const uint32_t c = (uint32_t)__popc(word);
@@ -3384,6 +3389,9 @@ __global__ __launch_bounds__(KW_THREADS) void kw_idset_expand_kernel(const uint3
         if (t == 0) s_base += all;
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(KW_THREADS) void kw_idset_expand_kernel(const uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ out, uint64_t cap) {
+    idset_expand_range(bits, 0, n_words, out, 0, cap);
 }
 
 // num_keyword_matches of a query with filter ids AND excluded ids AND several query_by fields: the first-order recurrence of

@@ -9,6 +9,7 @@
 #endif
 #include <cmath>
 #include "kw_kernels.hip.h"
+#include "kw_infix.hip.h"
 #include "kw_plan.hip.h"
 #include "kw_plan_digest.h"
 #include "kw_translate.h"
@@ -189,6 +190,10 @@ void tsgpu_destroy(tsgpu_ctx* ctx) {
     tsgpu_facet_destroy_all(ctx);
     tsgpu_groupby_destroy(ctx);
     for (auto& L : ctx->lanes) L.release();
+    for (auto& b : ctx->infix_buf) b.release();
+    std::atomic_store(&ctx->infix_test_snap, std::shared_ptr<const Snapshot>());
+    if (ctx->infix_stream) (void)hipStreamDestroy(ctx->infix_stream);
+    ctx->infix.clear();                              // (the staged vocabularies' device arrays go to the retire bin, drained below)
     std::atomic_store(&ctx->snap, std::shared_ptr<const Snapshot>());
     ctx->retire_bin->drain();
     deferred_frees().drain();
@@ -428,6 +433,13 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "doc_range_lo")) { ctx->doc_range_set = true; ctx->doc_range_lo = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 0xFFFFFFFFll); return ok(); }
     if (!strcmp(name, "doc_range_hi")) { ctx->doc_range_set = true; ctx->doc_range_hi = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 0xFFFFFFFFll); return ok(); }
     if (!strcmp(name, "kw_candidates_rank_fold")) { ctx->kw_candidates_rank_fold = value != 0; return ok(); }
+    if (!strcmp(name, "infix_compact_min_slots")) { ctx->infix_compact_min_slots = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1ll << 31); return ok(); }
+    if (!strcmp(name, "infix_timing")) { ctx->infix_timing = value != 0; return ok(); }
+    if (!strcmp(name, "infix_test_hold_snapshot")) {      // TESTS ONLY: 1 = infix batches run on the snapshot published NOW until 0 lets it go
+        std::atomic_store(&ctx->infix_test_snap, value != 0 ? ctx->snapshot() : std::shared_ptr<const Snapshot>());
+        return ok();
+    }
+    if (!strcmp(name, "infix_round_max_bytes")) { ctx->infix_round_max_bytes = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1ll << 36); return ok(); }
     if (!strcmp(name, "kw_mf_pipelined")) { ctx->kw_mf_pipelined = value != 0; return ok(); }
     if (!strcmp(name, "kw_count_touched")) { ctx->kw_count_touched = value != 0; return ok(); }
     if (!strcmp(name, "kw_plan_digest")) { ctx->kw_plan_digest = value != 0; return ok(); }
@@ -527,6 +539,21 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     std::lock_guard<std::mutex> lk(ctx->tm_mu);
     if (!strcmp(name, "kw_last_hit_groups")) { *out = ctx->kw_last_hit_groups; return ok(); }      // last keyword batch: find+score groups (0 = fused kernel)
     if (!strcmp(name, "kw_candidates_rank_launches")) { *out = ctx->kw_candidates_rank_launches; return ok(); }
+    // infix search (tsgpu_infix_search_batch, cumulative): vocabulary passes, live tokens they tested, tokens that matched (summed over the queries), posting lists united, rounds
+    if (!strcmp(name, "infix_scan_launches")) { *out = ctx->infix_scan_launches.load(); return ok(); }
+    if (!strcmp(name, "infix_tokens_scanned")) { *out = ctx->infix_tokens_scanned.load(); return ok(); }
+    if (!strcmp(name, "infix_tokens_matched")) { *out = ctx->infix_tokens_matched.load(); return ok(); }
+    if (!strcmp(name, "infix_lists_marked")) { *out = ctx->infix_lists_marked.load(); return ok(); }
+    if (!strcmp(name, "infix_rounds")) { *out = ctx->infix_rounds.load(); return ok(); }
+    if (!strcmp(name, "infix_tile_tokens")) { *out = INFIX_TILE_TOKENS; return ok(); }            // the scan kernel's tile: vocabulary slots per workgroup ...
+    if (!strcmp(name, "infix_tile_bytes")) { *out = INFIX_TILE_BYTES; return ok(); }              // ... and token bytes staged in LDS at a time
+    if (!strcmp(name, "infix_compactions")) { *out = ctx->infix_compactions.load(); return ok(); }       // (written by tsgpu_commit)
+    if (!strcmp(name, "infix_commit_uploaded_bytes")) { *out = ctx->infix_commit_uploaded_bytes.load(); return ok(); }
+    // under option "infix_timing" (cumulative, us of host wall clock with a stream sync behind each phase): vocabulary scans incl. the match lists' way back; union marks; exclusion, filter, count and expansion; ranking
+    if (!strcmp(name, "infix_scan_us")) { *out = ctx->infix_scan_us.load(); return ok(); }
+    if (!strcmp(name, "infix_mark_us")) { *out = ctx->infix_mark_us.load(); return ok(); }
+    if (!strcmp(name, "infix_expand_us")) { *out = ctx->infix_expand_us.load(); return ok(); }
+    if (!strcmp(name, "infix_rank_us")) { *out = ctx->infix_rank_us.load(); return ok(); }
     if (!strcmp(name, "kw_mf_pipelined_launches")) { *out = ctx->kw_mf_pipelined_launches; return ok(); }     // find launches served by kw_find_mf2_kernel
     if (!strcmp(name, "kw_last_hit_records")) { *out = ctx->kw_last_hit_records; return ok(); }    // hit-record capacity the last batch asked for
     if (!strcmp(name, "vec_overflow_rounds")) { *out = ctx->vec_overflow_rounds; return ok(); }
@@ -687,6 +714,7 @@ struct BatchPlanner {
     uint64_t now;
     std::vector<QueryCut> cut; std::vector<uint32_t> q_begin, q_cnt; std::vector<double> item_cost;
     std::vector<KwWorkItem> flat_work;                       // every query's items, contiguous, in query order
+    const uint64_t* wild_ids_dev = nullptr;                  // wildcard batch of the infix front: per query the DEVICE address of its n_filter filter ids (0: host ids as usual)
 
     // one or_iterator per token that exists in some field (kw_translate.h), in query order; returns the bytes of its lists
     uint64_t add_token(uint32_t i, QueryTokens& T, const KwTokenLists& tl, uint32_t len) {
@@ -721,7 +749,8 @@ struct BatchPlanner {
                 if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; return; }
                 A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
             }
-            if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);
+            if (wild_ids_dev && wild_ids_dev[i]) q.wild_ids = wild_ids_dev[i];      // (in.filter_ids is not a host address then)
+            else if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);
         }
         uint32_t n_ids = in.n_filter ? in.n_filter : ctx->num_docs;
         if (!vflat && ctx->doc_range_set) {
@@ -975,7 +1004,7 @@ struct BatchPlanner {
 }  // namespace
 
 static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query* queries, uint32_t n_queries, Plan& P, bool keep_ids, bool wildcard, const KwVFlat* vflat = nullptr,
-                      const uint16_t* present_elsewhere = nullptr) {
+                      const uint16_t* present_elsewhere = nullptr, const uint64_t* wild_ids_dev = nullptr) {
     static const bool plan_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
     const uint64_t tp0 = now_us();
     P.q.resize(n_queries);
@@ -983,6 +1012,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
     P.cutoff.assign(n_queries, 0);
     BatchPlanner B{ctx, snap, queries, n_queries, P, keep_ids, wildcard, vflat, present_elsewhere, tp0,
                    std::vector<QueryCut>(n_queries), std::vector<uint32_t>(n_queries, 0), std::vector<uint32_t>(n_queries, 0), std::vector<double>(n_queries, 0.0), {}};
+    B.wild_ids_dev = wild_ids_dev;
     const uint32_t min_par = ctx->plan_parallel_min_queries;
     const uint32_t min_slice = std::max<uint32_t>(8, min_par / 8);                      // (256 queries per slice at the default threshold)
     QuerySlices sl{n_queries, 1, 1};
@@ -1154,6 +1184,7 @@ struct BatchOpts {
     bool* ids_dev_done = nullptr;                     // consumer on the device (group_by, tsgpu_groupby.inc.h); not done (false) when a query's ids need the host's sort
     const uint16_t* present_elsewhere = nullptr;      // doc-range shard of a group whose members' dictionaries differ: per query, the tokens that exist on ANOTHER shard
                                                       // (missing here they are empty lists, not dropped tokens: kw_search_batch_masked, tsgpu_host.h); host planner
+    const uint64_t* wild_ids_dev = nullptr;           // wildcard batch of the infix front (tsgpu_infix_search_batch): the queries' filter ids are device arrays (KwQueryDev::wild_ids)
 };
 }
 static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* queries, uint32_t n_queries, tsgpu_hits* out, const BatchOpts& bo);
@@ -1875,7 +1906,7 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
             if (DP.on) ctx->kw_device_plans.fetch_add(1); else ctx->kw_device_plan_fallbacks.fetch_add(1);
             if (DP.on && keep_ids) P.ids_total = (DP.hit_blocks[0] + DP.hit_blocks[1]) * (uint64_t)BLOCK_IDS;
         }
-        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, bo.wildcard, bo.vflat, bo.present_elsewhere))) return rc;
+        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, bo.wildcard, bo.vflat, bo.present_elsewhere, bo.wild_ids_dev))) return rc;
         const uint64_t t_planned = now_us();
         if (out->k_stride < P.max_k) return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_search_batch: k_stride smaller than the largest topster_size");
         const uint32_t KS = out->k_stride;
@@ -2472,5 +2503,279 @@ int group_merge_keyword(tsgpu_ctx* ctx, const uint64_t* gathered, uint64_t shard
     return TSGPU_OK;
 }
 }  // namespace tsgpu
+
+// ---------------------------------------------------------------- infix search (kw_infix.hip.h)
+namespace {
+enum InfixBuf { IB_Q, IB_PAT, IB_MCNT, IB_MTERMS, IB_ITEMS, IB_BITS, IB_FBITS, IB_FOUND, IB_AUX, IB_SEGS, IB_FSLOT, IB_CHUNK, IB_IDS, IB_OFF, IB_NIDS };
+const uint64_t INFIX_MATCH_MAX_BYTES = 1ull << 30;         // match lists of one scan launch (capacity: vocabulary slots x 4 bytes per query); more queries -> more launches
+const uint32_t INFIX_MARK_BLOCKS = 64;                     // posting blocks per work item of the union
+const uint32_t INFIX_ROUND_MAX_QUERIES = 32768;            // (grid.y of the bitmap kernels)
+struct IndexViewLists { const ListDesc* lists; const BlockIds* blk_ids; const uint32_t* ids_payload; };     // what the union reads of a snapshot
+
+// the wildcard machinery over id lists that are on the device already: query j ranks the n_filter ids at wild[j]
+int infix_rank(tsgpu_ctx* ctx, const tsgpu_kw_query* q, uint32_t m, tsgpu_hits* out, const uint64_t* wild) {
+    struct CallerCount { std::atomic<int>& c; explicit CallerCount(std::atomic<int>& x) : c(x) { c.fetch_add(1); } ~CallerCount() { c.fetch_sub(1); } } cc(ctx->kw_callers);
+    CtxMuForVectorKeys vq_hold;
+    if (ctx->sort_keys_live.load(std::memory_order_relaxed) != 0 && names_vector_query_key(q, m)) vq_hold.take(ctx);
+    BatchOpts bo;
+    bo.wildcard = true;
+    bo.record_last = false;
+    bo.wild_ids_dev = wild;
+    LaneLock ll(ctx, tsgpu::tls_avoid_lane0() ? -2 : -1);
+    vq_hold.stream = ll.L->stream;
+    return kw_batch_on_lane(ctx, *ll.L, q, m, out, bo);
+}
+
+int infix_batch(tsgpu_ctx* ctx, const tsgpu_infix_query* queries, uint32_t n_queries, tsgpu_hits* out, uint32_t* n_tokens_matched, uint64_t* n_infix_ids, tsgpu_id_lists* lists) {
+    for (uint32_t i = 0; i < n_queries; i++) {
+        out->n_hits[i] = 0; out->status[i] = TSGPU_OK;
+        if (out->num_matched) out->num_matched[i] = 0;
+        if (out->search_cutoff) out->search_cutoff[i] = 0;
+        if (n_tokens_matched) n_tokens_matched[i] = 0;
+        if (n_infix_ids) n_infix_ids[i] = 0;
+    }
+    std::lock_guard<std::mutex> lk(ctx->infix_mu);             // one front at a time: it owns the stream and the scratch below
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->infix_stream) TSGPU_HIP_TRY(hipStreamCreateWithFlags(&ctx->infix_stream, hipStreamNonBlocking));
+    hipStream_t s = ctx->infix_stream;
+    DevBuf* B = ctx->infix_buf;
+    const std::shared_ptr<const Snapshot> held = std::atomic_load(&ctx->infix_test_snap);
+    const std::shared_ptr<const Snapshot> sn = held ? held : ctx->snapshot();
+    const uint64_t now = now_us();
+    const bool timing = ctx->infix_timing;
+    int rc;
+
+    // ---- the queries' own checks; the ones that pass, by field
+    std::vector<std::pair<uint32_t, uint32_t>> by_field;       // (field, query)
+    for (uint32_t i = 0; i < n_queries; i++) {
+        const tsgpu_infix_query& q = queries[i];
+        int st = TSGPU_OK;
+        if ((q.pattern_len && !q.pattern) || q.n_sort > TSGPU_MAX_SORT_KEYS || (q.n_filter && !q.filter_ids) || (q.n_excluded && !q.excluded_ids) ||
+            sn->infix.find(q.field_id) == sn->infix.end()) st = TSGPU_ERR_INVALID;
+        else if (q.pattern_len > TSGPU_MAX_INFIX_PATTERN) st = TSGPU_ERR_UNSUPPORTED;
+        else if ((st = check_sort_slots(ctx, q.sort, q.n_sort, false, false, nullptr)) != TSGPU_OK) {}
+        else if (q.deadline_us != 0 && now > q.deadline_us) { st = TSGPU_ERR_DEADLINE; if (out->search_cutoff) out->search_cutoff[i] = 1; }
+        out->status[i] = st;
+        if (st == TSGPU_OK) by_field.emplace_back(q.field_id, i);
+    }
+    std::stable_sort(by_field.begin(), by_field.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+
+    // ---- scan: one pass over a field's vocabulary for all of its queries -> per query the matching tokens' term ids -> the posting lists they have
+    std::vector<std::vector<uint32_t>> lists_of(n_queries);
+    for (size_t f0 = 0; f0 < by_field.size();) {
+        size_t f1 = f0;
+        while (f1 < by_field.size() && by_field[f1].first == by_field[f0].first) f1++;
+        const uint32_t field = by_field[f0].first;
+        const InfixVocabSnap& V = sn->infix.at(field);
+        const uint64_t t_scan = timing ? now_us() : 0;
+        if (V.n_slots != 0 && V.dev) {
+            const InfixVocabView view{V.dev->bytes.as<uint8_t>(), V.dev->byte_ptr.as<uint32_t>(), V.dev->term_id.as<uint32_t>(), V.dev->born.as<uint32_t>(), V.dev->died.as<uint32_t>(),
+                                      V.n_slots, V.epoch};
+            const uint64_t per_q = (uint64_t)V.n_slots * 4;
+            const size_t max_q = (size_t)std::max<uint64_t>(1, INFIX_MATCH_MAX_BYTES / per_q);
+            for (size_t g0 = f0; g0 < f1; g0 += max_q) {
+                const uint32_t ng = (uint32_t)std::min(max_q, f1 - g0);
+                std::vector<InfixQueryDev> dq(ng);
+                std::vector<uint8_t> pat;
+                for (uint32_t j = 0; j < ng; j++) {
+                    const tsgpu_infix_query& q = queries[by_field[g0 + j].second];
+                    dq[j] = InfixQueryDev{(uint32_t)pat.size(), q.pattern_len, q.max_extra_prefix, q.max_extra_suffix, j * V.n_slots, 0};
+                    pat.insert(pat.end(), q.pattern, q.pattern + q.pattern_len);
+                }
+                if ((rc = upload(B[IB_Q], dq.data(), dq.size() * sizeof(InfixQueryDev), s)) || (rc = upload(B[IB_PAT], pat.data(), pat.size(), s)) ||
+                    (rc = B[IB_MCNT].reserve((size_t)ng * 4)) || (rc = B[IB_MTERMS].reserve((size_t)ng * per_q))) return rc;
+                TSGPU_HIP_TRY(hipMemsetAsync(B[IB_MCNT].p, 0, (size_t)ng * 4, s));
+                hipLaunchKernelGGL(infix_scan_kernel, dim3((V.n_slots + INFIX_TILE_TOKENS - 1) / INFIX_TILE_TOKENS), dim3(INFIX_THREADS), 0, s, view, B[IB_Q].as<InfixQueryDev>(), ng,
+                                   B[IB_PAT].as<uint8_t>(), B[IB_MCNT].as<uint32_t>(), B[IB_MTERMS].as<uint32_t>());
+                TSGPU_HIP_TRY(hipGetLastError());
+                std::vector<uint32_t> cnt(ng);
+                TSGPU_HIP_TRY(hipMemcpyAsync(cnt.data(), B[IB_MCNT].p, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+                TSGPU_HIP_TRY(hipStreamSynchronize(s));
+                std::vector<std::vector<uint32_t>> terms(ng);
+                uint64_t matched = 0;
+                for (uint32_t j = 0; j < ng; j++) {
+                    if (cnt[j] > V.n_slots) return fail(TSGPU_ERR_DEVICE, "tsgpu_infix_search_batch: a match list beyond the vocabulary");
+                    matched += cnt[j];
+                    terms[j].resize(cnt[j]);
+                    if (cnt[j]) TSGPU_HIP_TRY(hipMemcpyAsync(terms[j].data(), B[IB_MTERMS].as<uint32_t>() + (size_t)j * V.n_slots, (size_t)cnt[j] * 4, hipMemcpyDeviceToHost, s));
+                }
+                TSGPU_HIP_TRY(hipStreamSynchronize(s));
+                ctx->infix_scan_launches.fetch_add(1); ctx->infix_tokens_scanned.fetch_add(V.n_live); ctx->infix_tokens_matched.fetch_add(matched);
+                for (uint32_t j = 0; j < ng; j++) {
+                    const uint32_t i = by_field[g0 + j].second;
+                    if (n_tokens_matched) n_tokens_matched[i] = cnt[j];
+                    for (uint32_t term : terms[j]) {                     // a matching token without a posting list contributes nothing (:3308-3313)
+                        const uint32_t h = sn->find_handle(field, term);
+                        if (h != 0xFFFFFFFFu && sn->h_lists[h].n_blocks != 0) lists_of[i].push_back(h);
+                    }
+                }
+            }
+        }
+        if (timing) ctx->infix_scan_us.fetch_add(now_us() - t_scan);
+        f0 = f1;
+    }
+
+    // ---- union, exclusion, filter, expansion and ranking, in rounds whose scratch fits
+    const uint32_t num_docs = sn->num_docs;
+    const uint64_t words = ((uint64_t)num_docs + 31) / 32;
+    std::vector<uint32_t> active;
+    for (uint32_t i = 0; i < n_queries; i++) if (!lists_of[i].empty() && words) active.push_back(i);
+    std::vector<std::vector<uint32_t>> ids_host(lists ? n_queries : 0);
+    const IndexViewLists ivl{sn->lists.as<ListDesc>(), sn->ar ? sn->ar->blk_ids.as<BlockIds>() : nullptr, sn->ar ? sn->ar->ids_payload.as<uint32_t>() : nullptr};
+    for (size_t a0 = 0; a0 < active.size();) {
+        size_t a1 = a0;
+        uint64_t bytes = 0, ids_total = 0;
+        std::vector<uint64_t> off_cap;                         // [nr] offsets, then [nr] capacities
+        std::vector<uint64_t> caps;
+        while (a1 < active.size() && a1 - a0 < INFIX_ROUND_MAX_QUERIES) {
+            const tsgpu_infix_query& q = queries[active[a1]];
+            uint64_t sum = 0;
+            for (uint32_t h : lists_of[active[a1]]) sum += sn->h_lists[h].n_ids;
+            const uint64_t cap = std::min<uint64_t>(sum, words * 32);          // (the bitmap's bits: an id in [num_docs, words * 32) is marked and expanded like any other)
+            const uint64_t need = words * 4 * (q.filter_ids ? 2 : 1) + cap * 4;
+            if (a1 > a0 && bytes + need > ctx->infix_round_max_bytes) break;
+            bytes += need; caps.push_back(cap); a1++;
+        }
+        const uint32_t nr = (uint32_t)(a1 - a0);
+        ctx->infix_rounds.fetch_add(1);
+        std::vector<InfixMarkItem> items;
+        std::vector<uint32_t> aux, fslot(nr, INFIX_NO_POS);
+        std::vector<InfixIdSeg> segs_f, segs_x;
+        uint32_t nf = 0;
+        uint64_t n_lists = 0;
+        for (uint32_t slot = 0; slot < nr; slot++) {
+            const uint32_t i = active[a0 + slot];
+            const tsgpu_infix_query& q = queries[i];
+            for (uint32_t h : lists_of[i]) {
+                const uint32_t nb = sn->h_lists[h].n_blocks;
+                for (uint32_t b = 0; b < nb; b += INFIX_MARK_BLOCKS) items.push_back(InfixMarkItem{slot, h, b, std::min(nb, b + INFIX_MARK_BLOCKS)});
+            }
+            n_lists += lists_of[i].size();
+            if (q.filter_ids) {
+                fslot[slot] = nf;
+                if (q.n_filter) { segs_f.push_back(InfixIdSeg{aux.size(), q.n_filter, nf}); aux.insert(aux.end(), q.filter_ids, q.filter_ids + q.n_filter); }
+                nf++;
+            }
+            if (q.n_excluded) { segs_x.push_back(InfixIdSeg{aux.size(), q.n_excluded, slot}); aux.insert(aux.end(), q.excluded_ids, q.excluded_ids + q.n_excluded); }
+            off_cap.push_back(ids_total);
+            ids_total += caps[slot];
+        }
+        off_cap.insert(off_cap.end(), caps.begin(), caps.end());
+        std::vector<InfixIdSeg> segs(segs_f);
+        segs.insert(segs.end(), segs_x.begin(), segs_x.end());
+        const uint32_t n_chunks = (uint32_t)((words + INFIX_EXPAND_WORDS - 1) / INFIX_EXPAND_WORDS);
+        if ((rc = B[IB_BITS].reserve((size_t)nr * words * 4)) || (rc = B[IB_FBITS].reserve((size_t)std::max<uint32_t>(nf, 1) * words * 4)) || (rc = B[IB_FOUND].reserve((size_t)nr * 8)) ||
+            (rc = upload(B[IB_ITEMS], items.data(), items.size() * sizeof(InfixMarkItem), s)) || (rc = upload(B[IB_AUX], aux.data(), aux.size() * 4, s)) ||
+            (rc = upload(B[IB_SEGS], segs.data(), segs.size() * sizeof(InfixIdSeg), s)) || (rc = upload(B[IB_FSLOT], fslot.data(), fslot.size() * 4, s)) ||
+            (rc = upload(B[IB_OFF], off_cap.data(), off_cap.size() * 8, s)) || (rc = B[IB_CHUNK].reserve((size_t)nr * n_chunks * 4)) ||
+            (rc = B[IB_IDS].reserve((size_t)std::max<uint64_t>(ids_total, 1) * 4)) || (rc = B[IB_NIDS].reserve((size_t)nr * 4))) return rc;
+        TSGPU_HIP_TRY(hipMemsetAsync(B[IB_BITS].p, 0, (size_t)nr * words * 4, s));
+        TSGPU_HIP_TRY(hipMemsetAsync(B[IB_FOUND].p, 0, (size_t)nr * 8, s));
+        if (nf) TSGPU_HIP_TRY(hipMemsetAsync(B[IB_FBITS].p, 0, (size_t)nf * words * 4, s));
+        uint32_t* bits = B[IB_BITS].as<uint32_t>();
+        uint64_t t_ph = 0;
+        if (timing) { TSGPU_HIP_TRY(hipStreamSynchronize(s)); t_ph = now_us(); }
+        if (!items.empty())
+            hipLaunchKernelGGL(infix_union_mark_kernel, dim3((uint32_t)items.size()), dim3(INFIX_THREADS), 0, s, B[IB_ITEMS].as<InfixMarkItem>(), ivl.lists, ivl.blk_ids, ivl.ids_payload, bits,
+                               words, B[IB_FOUND].as<unsigned long long>());
+        if (timing) { TSGPU_HIP_TRY(hipStreamSynchronize(s)); const uint64_t t = now_us(); ctx->infix_mark_us.fetch_add(t - t_ph); t_ph = t; }
+        if (!segs_f.empty())
+            hipLaunchKernelGGL(infix_idlist_set_kernel, dim3((uint32_t)segs_f.size(), 8), dim3(INFIX_THREADS), 0, s, B[IB_AUX].as<uint32_t>(), B[IB_SEGS].as<InfixIdSeg>(), B[IB_FBITS].as<uint32_t>(), words);
+        if (nf)
+            hipLaunchKernelGGL(infix_bits_and_kernel, dim3((uint32_t)((words + INFIX_THREADS - 1) / INFIX_THREADS), nr), dim3(INFIX_THREADS), 0, s, bits, B[IB_FBITS].as<uint32_t>(),
+                               B[IB_FSLOT].as<uint32_t>(), words);
+        if (!segs_x.empty())
+            hipLaunchKernelGGL(infix_idlist_clear_kernel, dim3((uint32_t)segs_x.size(), 8), dim3(INFIX_THREADS), 0, s, B[IB_AUX].as<uint32_t>(), B[IB_SEGS].as<InfixIdSeg>() + segs_f.size(), bits, words);
+        hipLaunchKernelGGL(infix_count_kernel, dim3(n_chunks, nr), dim3(INFIX_THREADS), 0, s, bits, words, B[IB_CHUNK].as<uint32_t>());
+        hipLaunchKernelGGL(infix_expand_kernel, dim3(n_chunks, nr), dim3(INFIX_THREADS), 0, s, bits, words, B[IB_CHUNK].as<uint32_t>(), B[IB_IDS].as<uint32_t>(), B[IB_OFF].as<uint64_t>(),
+                           B[IB_OFF].as<uint64_t>() + nr, B[IB_NIDS].as<uint32_t>());
+        TSGPU_HIP_TRY(hipGetLastError());
+        std::vector<uint64_t> found(nr);
+        std::vector<uint32_t> nids(nr);
+        TSGPU_HIP_TRY(hipMemcpyAsync(found.data(), B[IB_FOUND].p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
+        TSGPU_HIP_TRY(hipMemcpyAsync(nids.data(), B[IB_NIDS].p, (size_t)nr * 4, hipMemcpyDeviceToHost, s));
+        TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        if (timing) ctx->infix_expand_us.fetch_add(now_us() - t_ph);
+        ctx->infix_lists_marked.fetch_add(n_lists);
+
+        // the surviving ids: to the caller's list object, and — still on the device — to the wildcard ranking
+        std::vector<tsgpu_kw_query> kq;
+        std::vector<uint64_t> wild;
+        std::vector<uint32_t> q_of;
+        for (uint32_t slot = 0; slot < nr; slot++) {
+            const uint32_t i = active[a0 + slot];
+            const tsgpu_infix_query& q = queries[i];
+            if (nids[slot] > caps[slot]) return fail(TSGPU_ERR_DEVICE, "tsgpu_infix_search_batch: an id list beyond its bound");
+            if (n_infix_ids) n_infix_ids[i] = found[slot];
+            if (nids[slot] == 0) continue;
+            const uint32_t* d_ids = B[IB_IDS].as<uint32_t>() + off_cap[slot];
+            if (lists) { ids_host[i].resize(nids[slot]); TSGPU_HIP_TRY(hipMemcpyAsync(ids_host[i].data(), d_ids, (size_t)nids[slot] * 4, hipMemcpyDeviceToHost, s)); }
+            tsgpu_kw_query k;
+            memset(&k, 0, sizeof k);
+            k.n_sort = q.n_sort;
+            for (uint32_t x = 0; x < q.n_sort; x++) k.sort[x] = q.sort[x];
+            k.topster_size = q.topster_size;
+            k.filter_ids = d_ids;                                  // (a device address: read through KwQueryDev::wild_ids only)
+            k.n_filter = nids[slot];
+            k.deadline_us = q.deadline_us;
+            kq.push_back(k); wild.push_back((uint64_t)(uintptr_t)d_ids); q_of.push_back(i);
+        }
+        if (lists) TSGPU_HIP_TRY(hipStreamSynchronize(s));
+        const uint32_t m = (uint32_t)kq.size();
+        const uint64_t t_rank = timing ? now_us() : 0;
+        if (m == n_queries) { if ((rc = infix_rank(ctx, kq.data(), m, out, wild.data()))) return rc; }       // every query of the call, in order: straight into the caller's arrays
+        else if (m) {
+            const size_t ks = out->k_stride;
+            std::vector<uint64_t> keys(m * ks), nm(m);
+            std::vector<int64_t> scores(m * ks * 3), tm(m * ks);
+            std::vector<float> vd(m * ks);
+            std::vector<int8_t> msi(m * ks);
+            std::vector<uint32_t> nh(m);
+            std::vector<int32_t> st(m), co(m);
+            tsgpu_hits tmp{TSGPU_MEM_HOST, out->k_stride, keys.data(), scores.data(), tm.data(), vd.data(), msi.data(), nh.data(), nm.data(), st.data(), co.data()};
+            if ((rc = infix_rank(ctx, kq.data(), m, &tmp, wild.data()))) return rc;
+            for (uint32_t j = 0; j < m; j++) {
+                const uint32_t i = q_of[j];
+                const size_t n = std::min<size_t>(nh[j], ks);
+                std::copy(keys.begin() + j * ks, keys.begin() + j * ks + n, out->keys + i * ks);
+                std::copy(scores.begin() + j * ks * 3, scores.begin() + (j * ks + n) * 3, out->scores + i * ks * 3);
+                if (out->text_match) std::copy(tm.begin() + j * ks, tm.begin() + j * ks + n, out->text_match + i * ks);
+                if (out->vector_distance) std::copy(vd.begin() + j * ks, vd.begin() + j * ks + n, out->vector_distance + i * ks);
+                if (out->match_score_index) std::copy(msi.begin() + j * ks, msi.begin() + j * ks + n, out->match_score_index + i * ks);
+                out->n_hits[i] = nh[j]; out->status[i] = st[j];
+                if (out->num_matched) out->num_matched[i] = nm[j];
+                if (out->search_cutoff) out->search_cutoff[i] = co[j];
+            }
+        }
+        if (timing) ctx->infix_rank_us.fetch_add(now_us() - t_rank);
+        a0 = a1;
+    }
+    if (lists) {
+        lists->begin.assign((size_t)n_queries + 1, 0);
+        for (uint32_t i = 0; i < n_queries; i++) { lists->ids.insert(lists->ids.end(), ids_host[i].begin(), ids_host[i].end()); lists->begin[i + 1] = lists->ids.size(); }
+    }
+    return TSGPU_OK;
+}
+}  // namespace
+
+extern "C" int tsgpu_infix_search_batch(tsgpu_ctx* ctx, const tsgpu_infix_query* queries, uint32_t n_queries, tsgpu_hits* out, uint32_t* n_tokens_matched, uint64_t* n_infix_ids,
+                                        tsgpu_id_lists** ids_out) {
+    if (ids_out) *ids_out = nullptr;
+    if (!ctx || !out) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_search_batch: NULL argument");
+    if (out->mem != TSGPU_MEM_HOST) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_infix_search_batch: host outputs only");
+    if (ctx->doc_range_set) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_infix_search_batch: not served on a doc-range shard");
+    std::unique_ptr<tsgpu_id_lists> lists;
+    if (ids_out) { lists.reset(new (std::nothrow) tsgpu_id_lists); if (!lists) return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_search_batch: host allocation failed"); }
+    try {
+        if (lists) lists->begin.assign((size_t)n_queries + 1, 0);
+        if (n_queries) {
+            if (!queries) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_search_batch: queries is NULL");
+            if (!out->keys || !out->scores || !out->n_hits || !out->status) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_search_batch: missing output arrays");
+            if (const int rc = infix_batch(ctx, queries, n_queries, out, n_tokens_matched, n_infix_ids, lists.get())) return rc;
+        }
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_search_batch: host allocation failed"); }
+    if (ids_out) *ids_out = lists.release();
+    return ok();
+}
 
 #include "tsgpu_groupby.inc.h"

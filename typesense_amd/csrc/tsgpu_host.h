@@ -282,7 +282,41 @@ struct IdDirRef {
     ~IdDirRef() { if (pool) pool->give(slot); }
 };
 
+// VOCABULARY MIRROR of an infix-enabled field (Index::infix_index, src/index.cpp:852-856, 7352-7356; scanned by infix_scan_kernel, kw_infix.hip.h): the token
+// bytes as one arena, a CSR byte_ptr[n + 1] and term_id[n], plus born[n] / died[n] — slot i is live for the snapshot of epoch e iff born[i] <= e < died[i].
+// Consecutive snapshots SHARE the device arrays: a commit appends the new slots behind the published ones (a replaced token gets a new slot) and writes
+// `died` of the slots it retires — 4 bytes per tombstone, and a value greater than every older snapshot's epoch, so a search that started before the commit
+// still sees its own vocabulary. The arrays are written afresh (live slots only) when they run out of room, when the vocabulary was replaced
+// (tsgpu_infix_tokens_load) and when the dead slots outnumber the live ones (and option "infix_compact_min_slots", default 1024): a compaction.
+struct InfixVocabDev {
+    DevBuf bytes, byte_ptr, term_id, born, died;
+    uint64_t cap_bytes = 0;
+    uint32_t cap_slots = 0;
+    std::shared_ptr<RetireBin> bin;
+    InfixVocabDev() = default;
+    InfixVocabDev(const InfixVocabDev&) = delete;
+    InfixVocabDev& operator=(const InfixVocabDev&) = delete;
+    ~InfixVocabDev() {
+        DevBuf* b[] = {&bytes, &byte_ptr, &term_id, &born, &died};
+        for (DevBuf* x : b) { if (bin) bin->put(*x); else x->release(); }
+    }
+};
+struct InfixVocabSnap { std::shared_ptr<InfixVocabDev> dev; uint32_t n_slots = 0, epoch = 0; uint64_t n_live = 0, n_bytes = 0; };
+// the host side (under ctx->mu): the staged vocabulary — every upsert / erase is applied here at once, stamped with the epoch of the NEXT commit
+struct InfixFieldHost {
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> byte_ptr{0u}, term_id, born, died;
+    std::unordered_map<uint32_t, uint32_t> slot_of;  // live term id -> its slot
+    std::vector<uint32_t> retired;                   // published slots whose `died` changed since the last commit
+    std::shared_ptr<InfixVocabDev> dev;
+    uint32_t epoch = 0;                              // of the last commit
+    uint32_t uploaded_slots = 0;
+    uint64_t uploaded_bytes = 0;
+    bool rebuild = true;                             // the next commit writes fresh arrays
+};
+
 struct Snapshot {            // immutable view of all posting lists; published by tsgpu_commit, shared (RCU) by the searches that started on it
+    std::unordered_map<uint32_t, InfixVocabSnap> infix;             // the infix-enabled fields' vocabularies as of this snapshot
     std::shared_ptr<ArenaSet> ar;
     std::shared_ptr<IdDirPool> dir_pool;                             // id directories of the long lists (null: none)
     std::vector<std::shared_ptr<IdDirRef>> dir_of;                   // by list handle (shorter than h_lists / null entries: no directory)
@@ -617,6 +651,19 @@ struct tsgpu_ctx {
     uint32_t vec_count_rescored = 0;
     uint64_t vec_prefilter_fallbacks = 0;            // query groups the bf16 bracket could not separate (ran on the fp32 scan)
     uint64_t vec_overflow_rounds = 0;                // pass-2 repeats caused by candidate overflow (introspection)
+
+    // infix search (tsgpu_infix_*; kw_infix.hip.h): the staged vocabularies (under mu) and the front's stream + scratch (one infix batch at a time: infix_mu)
+    std::unordered_map<uint32_t, tsgpu::InfixFieldHost> infix;
+    uint32_t infix_compact_min_slots = 1024;         // option: dead slots below this never trigger a vocabulary compaction
+    uint64_t infix_round_max_bytes = 2ull << 30;     // option: bitmap + id-list scratch of one round of a batch (a batch that needs more runs in rounds)
+    std::atomic<uint64_t> infix_compactions{0}, infix_commit_uploaded_bytes{0};      // counters (written by tsgpu_commit)
+    bool infix_timing = false;                       // option (measurement only): a stream sync behind every phase of the front, host wall clock per phase in the counters below
+    std::atomic<uint64_t> infix_scan_us{0}, infix_mark_us{0}, infix_expand_us{0}, infix_rank_us{0};
+    std::shared_ptr<const tsgpu::Snapshot> infix_test_snap;      // TESTS ONLY (option "infix_test_hold_snapshot"): the snapshot infix batches run on instead of the published one (std::atomic_load / atomic_store)
+    std::mutex infix_mu;
+    hipStream_t infix_stream = nullptr;
+    tsgpu::DevBuf infix_buf[16];
+    std::atomic<uint64_t> infix_scan_launches{0}, infix_tokens_scanned{0}, infix_tokens_matched{0}, infix_lists_marked{0}, infix_rounds{0};
 
     std::unordered_map<uint32_t, tsgpu::VecField*> vec_fields;
     std::unordered_map<uint32_t, tsgpu::FacetField*> facet_fields;

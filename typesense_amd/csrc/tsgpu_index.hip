@@ -135,6 +135,18 @@ void split_open(TermHost& t, uint32_t id) {
     open_block(t, id <= t.pl.blk_last[b] ? (int64_t)b : (int64_t)b + 1);
 }
 
+// ---- infix vocabulary, host side of one staged change; e = the epoch of the next commit
+void infix_retire(InfixFieldHost& f, uint32_t slot, uint32_t e) {
+    f.died[slot] = e;
+    if (slot < f.uploaded_slots) f.retired.push_back(slot);
+}
+void infix_append(InfixFieldHost& f, uint32_t term_id, const uint8_t* bytes, uint32_t len, uint32_t e) {
+    f.slot_of[term_id] = (uint32_t)f.term_id.size();
+    f.bytes.insert(f.bytes.end(), bytes, bytes + len);
+    f.byte_ptr.push_back((uint32_t)f.bytes.size());
+    f.term_id.push_back(term_id); f.born.push_back(e); f.died.push_back(0xFFFFFFFFu);
+}
+
 }  // namespace
 
 extern "C" {
@@ -146,6 +158,80 @@ int tsgpu_field_create(tsgpu_ctx* ctx, uint32_t field_id, int is_array) {
     ctx->dirty_fields = true;
     ctx->dirty = true;
     return ok();
+}
+
+// ---- infix vocabulary (staged here, published by tsgpu_commit: infix_commit above)
+int tsgpu_infix_enable(tsgpu_ctx* ctx, uint32_t field_id) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->fields.find(field_id) == ctx->fields.end()) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_infix_enable: unknown field (call tsgpu_field_create)");
+    try { (void)ctx->infix[field_id]; } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_enable: host allocation failed"); }
+    ctx->dirty = true;
+    return ok();
+}
+
+int tsgpu_infix_tokens_load(tsgpu_ctx* ctx, uint32_t field_id, uint32_t n_tokens, const uint32_t* term_ids, const uint64_t* byte_ptr, const uint8_t* bytes) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    if (n_tokens && (!term_ids || !byte_ptr || !bytes)) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_tokens_load: NULL array");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->infix.find(field_id);
+    if (it == ctx->infix.end()) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_tokens_load: not an infix field (call tsgpu_infix_enable)");
+    for (uint32_t i = 0; i < n_tokens; i++) if (byte_ptr[i + 1] <= byte_ptr[i]) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_tokens_load: a token has no bytes");
+    if (n_tokens && byte_ptr[n_tokens] - byte_ptr[0] > 0xFFFFFFF0ull) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_infix_tokens_load: a vocabulary beyond 4 GiB");
+    try {
+        InfixFieldHost f;
+        f.epoch = it->second.epoch;
+        for (uint32_t i = 0; i < n_tokens; i++) {
+            if (f.slot_of.count(term_ids[i])) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_tokens_load: a term id occurs twice");
+            infix_append(f, term_ids[i], bytes + byte_ptr[i], (uint32_t)(byte_ptr[i + 1] - byte_ptr[i]), f.epoch + 1);
+        }
+        it->second = std::move(f);
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_tokens_load: host allocation failed"); }
+    ctx->dirty = true;
+    return ok();
+}
+
+int tsgpu_infix_token_upsert(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, const uint8_t* bytes, uint32_t len) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    if (!bytes || len == 0) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_token_upsert: a token has at least one byte");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->infix.find(field_id);
+    if (it == ctx->infix.end()) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_token_upsert: not an infix field (call tsgpu_infix_enable)");
+    InfixFieldHost& f = it->second;
+    if (f.bytes.size() + (uint64_t)len > 0xFFFFFFF0ull || f.term_id.size() >= 0xFFFFFFF0ull) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_infix_token_upsert: a vocabulary beyond 4 GiB");
+    try {
+        auto old = f.slot_of.find(term_id);
+        if (old != f.slot_of.end()) {
+            const uint32_t o = old->second;
+            if (f.byte_ptr[o + 1] - f.byte_ptr[o] == len && !memcmp(f.bytes.data() + f.byte_ptr[o], bytes, len)) return ok();      // (the token the field holds already)
+            infix_retire(f, o, f.epoch + 1);
+        }
+        infix_append(f, term_id, bytes, len, f.epoch + 1);
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_token_upsert: host allocation failed"); }
+    ctx->dirty = true;
+    return ok();
+}
+
+int tsgpu_infix_token_erase(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id) {
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->infix.find(field_id);
+    if (it == ctx->infix.end()) return fail(TSGPU_ERR_INVALID, "tsgpu_infix_token_erase: not an infix field (call tsgpu_infix_enable)");
+    InfixFieldHost& f = it->second;
+    auto old = f.slot_of.find(term_id);
+    if (old == f.slot_of.end()) return ok();              // (erasing what is not there: nothing to do, like std::set::erase)
+    try { infix_retire(f, old->second, f.epoch + 1); } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_token_erase: host allocation failed"); }
+    f.slot_of.erase(old);
+    ctx->dirty = true;
+    return ok();
+}
+
+uint64_t tsgpu_infix_num_tokens(tsgpu_ctx* ctx, uint32_t field_id) {
+    if (!ctx) return 0;
+    const std::shared_ptr<const Snapshot> sn = ctx->snapshot();
+    if (!sn) return 0;
+    auto it = sn->infix.find(field_id);
+    return it == sn->infix.end() ? 0 : it->second.n_live;
 }
 
 int tsgpu_term_upsert(tsgpu_ctx* ctx, uint32_t field_id, uint32_t term_id, const uint32_t* ids, const uint32_t* offset_index,
@@ -466,6 +552,69 @@ int build_id_directories(tsgpu_ctx* ctx, Snapshot& s, const Snapshot* cur, const
     return TSGPU_OK;
 }
 
+// ---- vocabulary mirrors of the infix-enabled fields (tsgpu_host.h: InfixVocabDev) -----------------------------------------------------------
+// Brings every field's device arrays up to the host's staged state and enters them into the snapshot being built (called last before it is published).
+// Uploads the appended tail (bytes, byte_ptr, term_id, born, died of the new slots) and 4 bytes per retired slot; everything only after a
+// tsgpu_infix_tokens_load, when the arrays are full (they are allocated half as large again) and at a compaction.
+int infix_commit(tsgpu_ctx* ctx, Snapshot& s) {
+    uint64_t uploaded = 0;
+    for (auto& fe : ctx->infix) {
+        InfixFieldHost& f = fe.second;
+        const uint32_t e = f.epoch + 1;
+        uint32_t n = (uint32_t)f.term_id.size();
+        const uint32_t live = (uint32_t)f.slot_of.size(), dead = n - live;
+        const bool changed = f.rebuild || n != f.uploaded_slots || !f.retired.empty();
+        if (!f.rebuild && changed && dead >= ctx->infix_compact_min_slots && dead > live) {          // compaction: the live slots alone, in slot order
+            InfixFieldHost c;
+            std::vector<std::pair<uint32_t, uint32_t>> order;                                        // (slot, term)
+            for (const auto& kv : f.slot_of) order.emplace_back(kv.second, kv.first);
+            std::sort(order.begin(), order.end());
+            for (const auto& o : order) infix_append(c, o.second, f.bytes.data() + f.byte_ptr[o.first], f.byte_ptr[o.first + 1] - f.byte_ptr[o.first], e);
+            f.bytes.swap(c.bytes); f.byte_ptr.swap(c.byte_ptr); f.term_id.swap(c.term_id); f.born.swap(c.born); f.died.swap(c.died); f.slot_of.swap(c.slot_of);
+            f.rebuild = true;
+            n = live;
+            ctx->infix_compactions++;
+        }
+        if (changed) {
+            const uint64_t nb = f.bytes.size();
+            const bool fresh = f.rebuild || !f.dev || n > f.dev->cap_slots || nb > f.dev->cap_bytes;
+            int rc = TSGPU_OK;
+            if (fresh) {
+                std::shared_ptr<InfixVocabDev> d = std::make_shared<InfixVocabDev>();
+                d->bin = ctx->retire_bin;
+                d->cap_slots = n + n / 2 + 256; d->cap_bytes = nb + nb / 2 + 4096;
+                if ((rc = d->bytes.reserve(d->cap_bytes + 32)) || (rc = d->byte_ptr.reserve(((size_t)d->cap_slots + 1) * 4)) || (rc = d->term_id.reserve((size_t)d->cap_slots * 4)) ||
+                    (rc = d->born.reserve((size_t)d->cap_slots * 4)) || (rc = d->died.reserve((size_t)d->cap_slots * 4))) { f.rebuild = true; return rc; }
+                f.dev = d; f.uploaded_slots = 0; f.uploaded_bytes = 0; f.retired.clear(); f.rebuild = true;      // (until the uploads below have succeeded)
+            }
+            InfixVocabDev& d = *f.dev;
+            const uint32_t a = f.uploaded_slots;
+            if (nb > f.uploaded_bytes) TSGPU_HIP_TRY(hipMemcpy(d.bytes.as<uint8_t>() + f.uploaded_bytes, f.bytes.data() + f.uploaded_bytes, nb - f.uploaded_bytes, hipMemcpyHostToDevice));
+            if (n > a || fresh) TSGPU_HIP_TRY(hipMemcpy(d.byte_ptr.as<uint32_t>() + a, f.byte_ptr.data() + a, ((size_t)n - a + 1) * 4, hipMemcpyHostToDevice));
+            if (n > a) {
+                TSGPU_HIP_TRY(hipMemcpy(d.term_id.as<uint32_t>() + a, f.term_id.data() + a, ((size_t)n - a) * 4, hipMemcpyHostToDevice));
+                TSGPU_HIP_TRY(hipMemcpy(d.born.as<uint32_t>() + a, f.born.data() + a, ((size_t)n - a) * 4, hipMemcpyHostToDevice));
+                TSGPU_HIP_TRY(hipMemcpy(d.died.as<uint32_t>() + a, f.died.data() + a, ((size_t)n - a) * 4, hipMemcpyHostToDevice));
+            }
+            uploaded += (nb - f.uploaded_bytes) + ((uint64_t)n - a) * 16 + 4;
+            if (f.retired.size() > 64) {             // many tombstones: the published part of `died` in one copy (the values of the other slots are what they were)
+                TSGPU_HIP_TRY(hipMemcpy(d.died.p, f.died.data(), (size_t)a * 4, hipMemcpyHostToDevice));
+                uploaded += (uint64_t)a * 4;
+            } else {
+                for (uint32_t slot : f.retired) TSGPU_HIP_TRY(hipMemcpy(d.died.as<uint32_t>() + slot, &f.died[slot], 4, hipMemcpyHostToDevice));
+                uploaded += f.retired.size() * 4;
+            }
+            f.retired.clear();
+            f.uploaded_slots = n; f.uploaded_bytes = nb; f.rebuild = false;
+        }
+        f.epoch = e;
+        InfixVocabSnap& v = s.infix[fe.first];
+        v.dev = f.dev; v.n_slots = f.uploaded_slots; v.epoch = e; v.n_live = f.slot_of.size(); v.n_bytes = f.uploaded_bytes;
+    }
+    ctx->infix_commit_uploaded_bytes = uploaded;
+    return TSGPU_OK;
+}
+
 // everything re-packed into fresh arenas (first commit, compaction, or the tails ran out of room)
 int commit_full(tsgpu_ctx* ctx) {
     std::shared_ptr<Snapshot> sp = std::make_shared<Snapshot>();
@@ -546,6 +695,7 @@ int commit_full(tsgpu_ctx* ctx) {
     if (!ctx->num_docs_set) ctx->num_docs = std::max(ctx->num_docs, order.empty() ? 0u : max_id + 1);
     s.num_docs = ctx->num_docs;
     ctx->commit_last_uploaded_bytes = (n_idw + n_pw) * 4 + n_slots * (4 + sizeof(BlockIds) + sizeof(BlockMeta)) + s.h_lists.size() * sizeof(ListDesc);
+    if ((rc = infix_commit(ctx, s))) return rc;
     ctx->commit_full_count++;
     std::atomic_store(&ctx->snap, std::shared_ptr<const Snapshot>(sp));      // publish
     return TSGPU_OK;
@@ -725,6 +875,7 @@ int commit_incremental(tsgpu_ctx* ctx, const std::shared_ptr<const Snapshot>& cu
     s.num_docs = ctx->num_docs;
     ctx->commit_last_uploaded_bytes = (st_idw.size() + st_pw.size()) * 4 + (st_last.size() + sc_dst.size()) * (4 + sizeof(BlockIds) + sizeof(BlockMeta)) + sc_dst.size() * 8 +
                                       s.h_lists.size() * sizeof(ListDesc);
+    if ((rc = infix_commit(ctx, s))) return rc;
     ctx->commit_incremental_count++;
     std::atomic_store(&ctx->snap, std::shared_ptr<const Snapshot>(sp));      // publish
     return TSGPU_OK;

@@ -76,6 +76,36 @@ class KwQuery:
             c.dropped_term_ids[i] = int(t)
 
 
+class InfixQuery:
+    """One (field, pattern) of do_infix_search's field loop (src/index.cpp:6144-6272): tsgpu_infix_query. filter_ids: None = no filter; an EMPTY array = a
+    filter that matched nothing."""
+
+    def __init__(self, field, pattern, max_extra_prefix=32767, max_extra_suffix=32767, sort=((B.SORT_TEXT_MATCH, 1, 0), (B.SORT_SEQ_ID, 1, 0)),
+                 topster_size=0, excluded_ids=None, filter_ids=None, deadline_us=0):
+        self.field, self.pattern = field, bytes(pattern)
+        self.max_extra_prefix, self.max_extra_suffix = max_extra_prefix, max_extra_suffix
+        self.sort, self.topster_size, self.deadline_us = tuple(sort), topster_size, deadline_us
+        self.excluded_ids = None if excluded_ids is None else _u32(excluded_ids)
+        self.filter_ids = None if filter_ids is None else _u32(filter_ids)
+        self._empty = np.zeros(1, np.uint32)             # (what a filter without ids points at: non-NULL)
+
+    def fill(self, c):
+        c.field_id = self.field
+        self._pat = C.create_string_buffer(self.pattern, max(len(self.pattern), 1))
+        c.pattern, c.pattern_len = C.cast(self._pat, C.c_void_p), len(self.pattern)
+        c.max_extra_prefix, c.max_extra_suffix = self.max_extra_prefix, self.max_extra_suffix
+        c.n_sort = len(self.sort)
+        for i, s in enumerate(self.sort[:3]):
+            c.sort[i].kind, c.sort[i].order, c.sort[i].column = s
+        c.topster_size = self.topster_size
+        if self.excluded_ids is not None and self.excluded_ids.size:
+            c.excluded_ids, c.n_excluded = self.excluded_ids.ctypes.data, self.excluded_ids.size
+        if self.filter_ids is not None:
+            c.filter_ids = (self.filter_ids if self.filter_ids.size else self._empty).ctypes.data
+            c.n_filter = self.filter_ids.size
+        c.deadline_us = self.deadline_us
+
+
 class Hits:
     """Host copy of tsgpu_hits for a batch (numpy, [n_queries, k_stride, ...])."""
 
@@ -350,6 +380,50 @@ class GpuIndex:
         finally:
             self.L.tsgpu_id_lists_free(lists)
         return hits, ids
+
+    # ---- infix search (Index::search_infix / do_infix_search) ----
+    def infix_enable(self, field_id):
+        self._ck(self.L.tsgpu_infix_enable(self.h, field_id))
+
+    def infix_tokens_load(self, field_id, term_ids, tokens):
+        """replaces the field's vocabulary: tokens[i] (bytes) under term_ids[i]; visible after commit()"""
+        term_ids = _u32(term_ids)
+        ptr = np.zeros(len(tokens) + 1, np.uint64)
+        ptr[1:] = np.cumsum([len(t) for t in tokens])
+        arena = np.frombuffer(b"".join(bytes(t) for t in tokens), np.uint8)
+        self._ck(self.L.tsgpu_infix_tokens_load(self.h, field_id, len(tokens), _vp(term_ids), _vp(ptr), _vp(arena)))
+
+    def infix_token_upsert(self, field_id, term_id, token):
+        token = bytes(token)
+        self._ck(self.L.tsgpu_infix_token_upsert(self.h, field_id, term_id, C.cast(C.create_string_buffer(token, max(len(token), 1)), C.c_void_p), len(token)))
+
+    def infix_token_erase(self, field_id, term_id):
+        self._ck(self.L.tsgpu_infix_token_erase(self.h, field_id, term_id))
+
+    def infix_num_tokens(self, field_id):
+        return int(self.L.tsgpu_infix_num_tokens(self.h, field_id))
+
+    def infix_search_batch(self, queries, k_stride=250, hits=None, want_ids=True):
+        """list[InfixQuery] -> (Hits, n_tokens_matched [n] u32, n_infix_ids [n] u64, per query the surviving ids ascending (None without want_ids))"""
+        n = len(queries)
+        arr = (B.InfixQueryC * max(n, 1))()
+        for i, q in enumerate(queries):
+            q.fill(arr[i])
+        hits = hits or Hits(n, k_stride)
+        hs = hits.c_struct()
+        n_tok, n_ids = np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        lists = C.c_void_p()
+        self._ck(self.L.tsgpu_infix_search_batch(self.h, C.cast(arr, C.c_void_p), n, C.byref(hs), _vp(n_tok), _vp(n_ids), C.byref(lists) if want_ids else None))
+        ids = None
+        if want_ids:
+            try:
+                ids = []
+                for q in range(n):
+                    cnt = self.L.tsgpu_id_lists_count(lists, q)
+                    ids.append(np.ctypeslib.as_array(self.L.tsgpu_id_lists_ids(lists, q), shape=(cnt,)).copy() if cnt else np.zeros(0, np.uint32))
+            finally:
+                self.L.tsgpu_id_lists_free(lists)
+        return hits, n_tok, n_ids, ids
 
     # ---- facet counting over matched ids (do_facets, hash-index branch) ----
     def keyword_search_grouped_batch(self, queries, groups, k_stride, g_stride=250, want_ids=False, want_registers=False):
