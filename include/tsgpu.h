@@ -454,6 +454,67 @@ typedef struct tsgpu_infix_query {
 int tsgpu_infix_search_batch(tsgpu_ctx* ctx, const tsgpu_infix_query* queries, uint32_t n_queries, tsgpu_hits* out,
                              uint32_t* n_tokens_matched, uint64_t* n_infix_ids, tsgpu_id_lists** ids_out);
 
+/* ------------------------------------------------------------------ phrase search (Index::do_phrase_search, src/index.cpp:5909-6086; Index::handle_exclusion, :6274-6324;
+ *                                                                    posting_list_t::get_phrase_matches, src/posting_list.cpp:1791-1825) */
+#define TSGPU_MAX_PHRASES 8             /* phrases per field of a query; more -> 501 for that query */
+#define TSGPU_MAX_PHRASE_FIELDS 4
+enum tsgpu_phrase_mode {
+    TSGPU_PHRASE_RANK = 0,              /* a query of phrases only (is_wildcard_query): fold, exclusion, filter, and every surviving id ranked (:5930-6080) */
+    TSGPU_PHRASE_IDS = 1,               /* a query that also has ordinary tokens (:6028-6032): the same up to the filter, no ranking; the ids are the filter_ids of its keyword search */
+    TSGPU_PHRASE_EXCLUDE = 2            /* -"..." (handle_exclusion, :6274-6324): the plain OR over fields and phrases; the caller merges it with the curated ids */
+};
+typedef struct tsgpu_phrase {
+    uint32_t n_tokens;                               /* 1..TSGPU_MAX_QUERY_TOKENS (0 -> 400, more -> 501) */
+    uint32_t term_ids[TSGPU_MAX_QUERY_TOKENS];       /* in phrase order; a token may repeat. A token without a posting list in the field skips the PHRASE (:5950-5953) */
+} tsgpu_phrase;
+/* One call of do_phrase_search (modes RANK, IDS) or handle_exclusion (EXCLUDE): the query_by fields in order, each with its phrases (q_phrases / q_exclude_tokens). */
+typedef struct tsgpu_phrase_query {
+    uint32_t mode;                                   /* tsgpu_phrase_mode */
+    uint32_t n_fields;                               /* 1..TSGPU_MAX_PHRASE_FIELDS */
+    uint32_t field_ids[TSGPU_MAX_PHRASE_FIELDS];
+    int32_t field_weights[TSGPU_MAX_PHRASE_FIELDS];  /* search_fields[i].weight (>= 0); read by RANK only */
+    uint32_t n_phrases[TSGPU_MAX_PHRASE_FIELDS];
+    tsgpu_phrase phrases[TSGPU_MAX_PHRASE_FIELDS][TSGPU_MAX_PHRASES];
+    uint32_t n_sort;                                 /* RANK only, as topster_size */
+    tsgpu_sort_by sort[TSGPU_MAX_SORT_KEYS];
+    uint32_t topster_size;                           /* as tsgpu_kw_query::topster_size */
+    const uint32_t* excluded_ids;                    /* ascending, host; may be NULL (:6012-6018); not read by EXCLUDE */
+    uint32_t n_excluded;
+    const uint32_t* filter_ids;                      /* ascending, host; NULL = no filter (the phrase ids stand for it, :6023-6026); non-NULL with n_filter == 0 = a filter that
+                                                        matched nothing; not read by EXCLUDE */
+    uint32_t n_filter;
+    uint64_t deadline_us;                            /* absolute epoch us; a query already late when the batch is planned reports 408 and search_cutoff = 1 */
+} tsgpu_phrase_query;
+
+/* Phrase search of a batch of queries, all on the device. Per field, in order (:5930-6010): every phrase whose tokens all have a posting list is intersected by
+ * the keyword path's planner and find kernels (a multi-token phrase = one AND item; their hit records stay on the device) and kw_phrase_mark_kernel tests each
+ * intersected document as get_phrase_matches does — per array element (a plain field is one element), over the longest non-descending prefix of every token's
+ * uint16 positions, some position p of token 0 with uint16(p + t) among token t's for every t (found_token_sequence, src/posting_list.cpp:1719-1789; a
+ * one-token phrase passes every id of its list). A phrase without matches is skipped; the others are folded acc = acc.empty() ? ids : acc AND ids (:5963-5981 —
+ * literally: after an intersection that came out empty the next phrase starts the field over). The first min(10 000, n) ids of a field's folded list get the
+ * text score 100000 + weight, the maximum over the fields (:5988-5995), every other id 0; the fields are ORed (:5997-6009), excluded_ids removed (:6012-6018),
+ * the filter ANDed (:6020-6026). RANK then ranks every surviving id by the wildcard kernels with that text score in the _text_match slot (:6034-6080): the top
+ * topster_size in Topster::sort() order, num_matched = ids ranked, every sort kind tsgpu_wildcard_search_batch serves. EXCLUDE: the OR over all fields and phrases
+ * whose tokens all exist, nothing else (:6300-6318).
+ *   out: the hits of the RANK queries; n_hits / status of every query. May be NULL when no query of the call has mode RANK: the first failing per-query status
+ *     is then the call's return code.
+ *   n_phrase_ids[q] (nullable): ids after exclusion and BEFORE the filter. Zero: no hits — an empty phrase result is never "a wildcard without a filter";
+ *   *ids_out (nullable): per query the surviving ids, ascending; a per-call object, tsgpu_id_lists_free.
+ * Per-query status: 400 a field the snapshot does not hold, n_fields outside 1..4, a phrase without tokens, an unknown mode, bad arguments; 501 more than
+ * TSGPU_MAX_PHRASES phrases in a field, more than TSGPU_MAX_QUERY_TOKENS tokens in a phrase, a sort slot the wildcard entry point refuses; 408 already late at
+ * planning (there is no deadline inside the front: every pass is bounded; the ranking checks it as the wildcard search does).
+ * NOT SERVED: the call answers 501 for out->mem != TSGPU_MEM_HOST (device outputs), on a doc-range shard (no shard form: a group member runs
+ * the CPU path) and with option "kw_two_kernels" = 0 (the adjacency kernel reads the find kernels' hit records); group_by (group_limit != 0) stays with the
+ * caller (csrc/host/tsgpu_phrase_shim.h answers 501); 1-query calls are not coalesced.
+ * Scratch (one bitmap of num_docs / 8 bytes per phrase, per field and per query, one more with a filter, the id lists) is bounded by option
+ * "phrase_round_max_bytes" (default 2 GiB): a batch that needs more runs in rounds (counter "phrase_rounds"). Counters: "phrase_items" ((query, field, phrase)
+ * items planned), "phrase_records_checked" / "phrase_records_matched" (hit records through the adjacency kernel), "phrase_syncs" (stream synchronisations of the
+ * front: one per round, one more per round with ids_out; the ranking's own are the wildcard search's). Safe with concurrent callers (one phrase batch at a time
+ * per context). MEASUREMENT ONLY: option "phrase_timing" = 1 puts a stream sync behind every phase (not counted in "phrase_syncs") and adds its host wall clock
+ * to "phrase_mark_us" (intersections + adjacency marks), "phrase_fold_us" (fold, OR, exclusion, filter, expansion, scores), "phrase_rank_us".
+ * TESTS ONLY: option "phrase_weight_cut" (default 10 000) = the number of ids per field that get the weight score. */
+int tsgpu_phrase_search_batch(tsgpu_ctx* ctx, const tsgpu_phrase_query* queries, uint32_t n_queries, tsgpu_hits* out, uint64_t* n_phrase_ids, tsgpu_id_lists** ids_out);
+
 /* ------------------------------------------------------------------ group_by: the DISTINCT Topster */
 /* One pass of the reference's two-pass grouped search (Index::run_search, src/index.cpp:2488-2760) through search_across_fields with
  * group_limit != 0 (src/index.cpp:5511-5520, 5546-5549) — or Index::search_wildcard's grouped loop (:6736-6760) — into

@@ -49,6 +49,22 @@ class InfixQueryC(C.Structure):
                 ("filter_ids", C.c_void_p), ("n_filter", C.c_uint32), ("deadline_us", C.c_uint64)]
 
 
+MAX_PHRASES, MAX_PHRASE_FIELDS = 8, 4
+PHRASE_RANK, PHRASE_IDS, PHRASE_EXCLUDE = 0, 1, 2
+
+
+class PhraseC(C.Structure):
+    _fields_ = [("n_tokens", C.c_uint32), ("term_ids", C.c_uint32 * MAX_QUERY_TOKENS)]
+
+
+class PhraseQueryC(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("n_fields", C.c_uint32), ("field_ids", C.c_uint32 * MAX_PHRASE_FIELDS), ("field_weights", C.c_int32 * MAX_PHRASE_FIELDS),
+                ("n_phrases", C.c_uint32 * MAX_PHRASE_FIELDS), ("phrases", PhraseC * MAX_PHRASES * MAX_PHRASE_FIELDS),
+                ("n_sort", C.c_uint32), ("sort", SortBy * 3), ("topster_size", C.c_uint32),
+                ("excluded_ids", C.c_void_p), ("n_excluded", C.c_uint32),
+                ("filter_ids", C.c_void_p), ("n_filter", C.c_uint32), ("deadline_us", C.c_uint64)]
+
+
 class HitsC(C.Structure):
     _fields_ = [("mem", C.c_int), ("k_stride", C.c_uint32),
                 ("keys", C.c_void_p), ("scores", C.c_void_p), ("text_match", C.c_void_p), ("vector_distance", C.c_void_p),
@@ -143,7 +159,7 @@ EXPORTS = [
     "tsgpu_abi_version", "tsgpu_create", "tsgpu_destroy", "tsgpu_last_error", "tsgpu_set_stream", "tsgpu_set_option", "tsgpu_get_counter", "tsgpu_device_bytes",
     "tsgpu_field_create", "tsgpu_term_upsert", "tsgpu_posting_upsert", "tsgpu_posting_erase", "tsgpu_terms_load_csr", "tsgpu_column_set", "tsgpu_set_num_docs", "tsgpu_sort_key_create_eval", "tsgpu_sort_key_create_vector_query", "tsgpu_sort_key_destroy", "tsgpu_commit",
     "tsgpu_term_num_ids", "tsgpu_term_download", "tsgpu_term_blocks_download", "tsgpu_keyword_search_batch", "tsgpu_wildcard_search_batch", "tsgpu_keyword_search_candidates_batch", "tsgpu_candidates_result_ids", "tsgpu_keep_result_ids", "tsgpu_result_ids",
-    "tsgpu_infix_enable", "tsgpu_infix_tokens_load", "tsgpu_infix_token_upsert", "tsgpu_infix_token_erase", "tsgpu_infix_num_tokens", "tsgpu_infix_search_batch",
+    "tsgpu_infix_enable", "tsgpu_infix_tokens_load", "tsgpu_infix_token_upsert", "tsgpu_infix_token_erase", "tsgpu_infix_num_tokens", "tsgpu_infix_search_batch", "tsgpu_phrase_search_batch",
     "tsgpu_keyword_search_batch_ids", "tsgpu_keyword_search_grouped_batch", "tsgpu_keyword_search_grouped_candidates_batch", "tsgpu_id_lists_count", "tsgpu_id_lists_ids", "tsgpu_id_lists_free", "tsgpu_facet_set", "tsgpu_facet_count_batch", "tsgpu_facet_count_grouped_batch", "tsgpu_facet_range_count_batch", "tsgpu_facet_stats_batch", "tsgpu_facet_value_set", "tsgpu_facet_value_count_batch",
     "tsgpu_vec_create", "tsgpu_vec_upsert", "tsgpu_vec_delete", "tsgpu_vec_get", "tsgpu_vec_count", "tsgpu_vec_knn_batch", "tsgpu_vec_knn_batch_filtered",
     "tsgpu_vec_hnsw_load", "tsgpu_vec_hnsw_enable", "tsgpu_vec_hnsw_build", "tsgpu_vec_hnsw_export", "tsgpu_vec_hnsw_search_batch", "tsgpu_vec_hnsw_search_batch_filtered", "tsgpu_vec_distances", "tsgpu_ip_distance", "tsgpu_vector_search_batch", "tsgpu_vector_search_batch_ids", "tsgpu_vector_search_batch_per_query", "tsgpu_vector_search_batch_per_query_ids", "tsgpu_hybrid_search_batch", "tsgpu_hybrid_fuse_batch", "tsgpu_keyword_aux_scores", "tsgpu_merge_shard_hits", "tsgpu_merge_shard_hits_device", "tsgpu_last_timings", "tsgpu_last_aux_timings", "tsgpu_kw_last_touched", "tsgpu_kw_lists_footprint",
@@ -217,6 +233,7 @@ def lib(path=None):
     L.tsgpu_infix_num_tokens.argtypes = [vp, u32]
     L.tsgpu_infix_num_tokens.restype = u64
     L.tsgpu_infix_search_batch.argtypes = [vp, vp, u32, C.POINTER(HitsC), vp, vp, C.POINTER(vp)]
+    L.tsgpu_phrase_search_batch.argtypes = [vp, vp, u32, C.POINTER(HitsC), vp, C.POINTER(vp)]
     L.tsgpu_id_lists_count.argtypes = [vp, u32]
     L.tsgpu_id_lists_count.restype = u64
     L.tsgpu_id_lists_ids.argtypes = [vp, u32]

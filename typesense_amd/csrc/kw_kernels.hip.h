@@ -225,6 +225,8 @@ struct KwQueryDev {                  // one search_across_fields call
     uint32_t pad3;
     uint64_t wild_ids;               // wildcard query whose n_filt filter ids are ALREADY on the device (the id list the infix front expanded, kw_infix.hip.h): their
                                      // address; 0 = the filter ids follow the excluded ids in the aux arena
+    uint64_t wild_tm;                // with wild_ids, the phrase front (kw_phrase.hip.h): device address of int64 tm[n_filt], the text-match value of filter id i
+                                     // (do_phrase_search's phrase_match_id_scores, src/index.cpp:6050); 0 = the constant of the wildcard / flat vector forms
 };
 
 // query_by over several fields (get_field_token_its, src/index.cpp:5598-5660): token t is the UNION over the fields of its
@@ -2393,7 +2395,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_wildcard_kernel(IndexView ix, c
                 if (q.vdist_abs) vd = fabsf(vd);
                 if (vd != vd || vd > q.vdist_thr) emit = false;
             }
-            if (emit) h = sort_scores(ix, q, seq_id, q.vdist ? 0 : 100, 0, false, vd);      // (text-match slot: 100 for q=*, 0 in the vector branch :3711)
+            if (emit) h = sort_scores(ix, q, seq_id, q.wild_tm ? (uint64_t)((const int64_t*)q.wild_tm)[idx] : (q.vdist ? 0 : 100), 0, false, vd);      // (text-match slot: 100 for q=*, 0 in the vector branch :3711, the id's phrase score :6050)
         }
         if constexpr (VQ) wave_vq_sort_patch(ix, q, seq_id, emit, h);
         uint32_t total;

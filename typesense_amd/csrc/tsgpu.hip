@@ -10,6 +10,7 @@
 #include <cmath>
 #include "kw_kernels.hip.h"
 #include "kw_infix.hip.h"
+#include "kw_phrase.hip.h"
 #include "kw_plan.hip.h"
 #include "kw_plan_digest.h"
 #include "kw_translate.h"
@@ -93,11 +94,16 @@ void launch_search(hipStream_t s, uint32_t n_work, const IndexView& v, const KwQ
 // two-kernel form: find (intersection -> hit records) then score (hit records -> partial top-K)
 template <int TMAX>
 void launch_find_score(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w, const KwPartials& part,
-                       const uint32_t* aux, uint32_t* ids_out, bool s2, uint32_t* hits, const uint64_t* hit_off, hipEvent_t mid_ev = nullptr, bool pair = false, bool plain = false, bool vq = false) {
+                       const uint32_t* aux, uint32_t* ids_out, bool s2, uint32_t* hits, const uint64_t* hit_off, hipEvent_t mid_ev = nullptr, bool pair = false, bool plain = false, bool vq = false,
+                       const PhraseMarkArgs* phrase = nullptr) {
     if (pair && v.touched) hipLaunchKernelGGL((kw_find2_kernel<TMAX, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);   // the byte-counting instantiation (measurement option)
     else if (pair) hipLaunchKernelGGL((kw_find2_kernel<TMAX>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else hipLaunchKernelGGL((kw_search_kernel<TMAX, 512, true, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     if (mid_ev) (void)hipEventRecord(mid_ev, s);           // find | score boundary of the batch's first group (tsgpu_timings::kw_find_ms)
+    if (phrase) {                                          // the phrase front (kw_phrase.hip.h): the adjacency check reads the hit records; nothing is scored
+        hipLaunchKernelGGL((kw_phrase_mark_kernel<TMAX, false>), dim3(n_work), dim3(PHRASE_THREADS), 0, s, v, q, w, part, hits, hit_off, *phrase);
+        return;
+    }
     if (vq) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_score_kernel<TMAX, decltype(c)::value, true, false, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off); });
     else if (cap == 512 && !s2 && plain && !ids_out) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, false, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (cap == 512 && !s2) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, false>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
@@ -118,12 +124,17 @@ void launch_search_mf_cap(int cap, hipStream_t s, uint32_t n_work, const IndexVi
 struct MfOrderedCount { const uint32_t* jobs = nullptr; uint32_t n_jobs = 0, table_first = 0; const KwWorkItem* work_all = nullptr; KwPartials part_all{}; };
 template <int TMAX>
 void launch_find_score_mf(int cap, hipStream_t s, uint32_t n_work, const IndexView& v, const KwQueryDev* q, const KwWorkItem* w, const KwPartials& part,
-                          const uint32_t* aux, uint32_t* ids_out, uint32_t* hits, const uint64_t* hit_off, const MfOrderedCount& oc, bool plain = false, int pipelined_lists = 0, bool vq = false) {
+                          const uint32_t* aux, uint32_t* ids_out, uint32_t* hits, const uint64_t* hit_off, const MfOrderedCount& oc, bool plain = false, int pipelined_lists = 0, bool vq = false,
+                          const PhraseMarkArgs* phrase = nullptr) {
     // pipelined_lists: 2 / 4 = the pipelined find kernel's instantiation that covers every multi-field query of the launch (kw_find_mf2.hip.h); 0 = kw_search_mf_kernel.
     // Same hit records either way.
     if (pipelined_lists == 2) hipLaunchKernelGGL((kw_find_mf2_kernel<TMAX, 2>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else if (pipelined_lists == 4) hipLaunchKernelGGL((kw_find_mf2_kernel<TMAX, 4>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, hits, hit_off);
     else hipLaunchKernelGGL((kw_search_mf_kernel<TMAX, 512, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
+    if (phrase) {                                          // (as in launch_find_score)
+        hipLaunchKernelGGL((kw_phrase_mark_kernel<TMAX, true>), dim3(n_work), dim3(PHRASE_THREADS), 0, s, v, q, w, part, hits, hit_off, *phrase);
+        return;
+    }
     if (oc.n_jobs) hipLaunchKernelGGL((kw_mf_ordered_count_kernel<TMAX>), dim3(oc.n_jobs), dim3(64), 0, s, q, oc.work_all, oc.part_all, hits, hit_off, oc.table_first, aux, oc.jobs);
     if (vq && cap == 512) hipLaunchKernelGGL((kw_score_kernel<TMAX, 512, true, true, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
     else if (vq) hipLaunchKernelGGL((kw_score_kernel<TMAX, 1024, true, true, false, true>), dim3(n_work), dim3(KW_THREADS), 0, s, v, q, w, part, aux, ids_out, hits, hit_off);
@@ -191,6 +202,7 @@ void tsgpu_destroy(tsgpu_ctx* ctx) {
     tsgpu_groupby_destroy(ctx);
     for (auto& L : ctx->lanes) L.release();
     for (auto& b : ctx->infix_buf) b.release();
+    for (auto& b : ctx->phrase_buf) b.release();
     std::atomic_store(&ctx->infix_test_snap, std::shared_ptr<const Snapshot>());
     if (ctx->infix_stream) (void)hipStreamDestroy(ctx->infix_stream);
     ctx->infix.clear();                              // (the staged vocabularies' device arrays go to the retire bin, drained below)
@@ -439,6 +451,9 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value) {
         std::atomic_store(&ctx->infix_test_snap, value != 0 ? ctx->snapshot() : std::shared_ptr<const Snapshot>());
         return ok();
     }
+    if (!strcmp(name, "phrase_round_max_bytes")) { ctx->phrase_round_max_bytes = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1ll << 36); return ok(); }
+    if (!strcmp(name, "phrase_weight_cut")) { ctx->phrase_weight_cut = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1ll << 24); return ok(); }      // TESTS ONLY
+    if (!strcmp(name, "phrase_timing")) { ctx->phrase_timing = value != 0; return ok(); }
     if (!strcmp(name, "infix_round_max_bytes")) { ctx->infix_round_max_bytes = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1ll << 36); return ok(); }
     if (!strcmp(name, "kw_mf_pipelined")) { ctx->kw_mf_pipelined = value != 0; return ok(); }
     if (!strcmp(name, "kw_count_touched")) { ctx->kw_count_touched = value != 0; return ok(); }
@@ -554,6 +569,16 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "infix_mark_us")) { *out = ctx->infix_mark_us.load(); return ok(); }
     if (!strcmp(name, "infix_expand_us")) { *out = ctx->infix_expand_us.load(); return ok(); }
     if (!strcmp(name, "infix_rank_us")) { *out = ctx->infix_rank_us.load(); return ok(); }
+    // phrase search (tsgpu_phrase_search_batch, cumulative): (query, field, phrase) items planned, hit records the adjacency kernel checked / matched, rounds, stream syncs of the front
+    if (!strcmp(name, "phrase_items")) { *out = ctx->phrase_items.load(); return ok(); }
+    if (!strcmp(name, "phrase_records_checked")) { *out = ctx->phrase_records_checked.load(); return ok(); }
+    if (!strcmp(name, "phrase_records_matched")) { *out = ctx->phrase_records_matched.load(); return ok(); }
+    if (!strcmp(name, "phrase_rounds")) { *out = ctx->phrase_rounds.load(); return ok(); }
+    if (!strcmp(name, "phrase_syncs")) { *out = ctx->phrase_syncs.load(); return ok(); }
+    // under option "phrase_timing" (cumulative, us of host wall clock with a stream sync behind each phase): intersections + adjacency marks; fold, field OR, exclusion, filter, expansion, scores; ranking
+    if (!strcmp(name, "phrase_mark_us")) { *out = ctx->phrase_mark_us.load(); return ok(); }
+    if (!strcmp(name, "phrase_fold_us")) { *out = ctx->phrase_fold_us.load(); return ok(); }
+    if (!strcmp(name, "phrase_rank_us")) { *out = ctx->phrase_rank_us.load(); return ok(); }
     if (!strcmp(name, "kw_mf_pipelined_launches")) { *out = ctx->kw_mf_pipelined_launches; return ok(); }     // find launches served by kw_find_mf2_kernel
     if (!strcmp(name, "kw_last_hit_records")) { *out = ctx->kw_last_hit_records; return ok(); }    // hit-record capacity the last batch asked for
     if (!strcmp(name, "vec_overflow_rounds")) { *out = ctx->vec_overflow_rounds; return ok(); }
@@ -715,6 +740,7 @@ struct BatchPlanner {
     std::vector<QueryCut> cut; std::vector<uint32_t> q_begin, q_cnt; std::vector<double> item_cost;
     std::vector<KwWorkItem> flat_work;                       // every query's items, contiguous, in query order
     const uint64_t* wild_ids_dev = nullptr;                  // wildcard batch of the infix front: per query the DEVICE address of its n_filter filter ids (0: host ids as usual)
+    const uint64_t* wild_tm_dev = nullptr;                   // ... of the phrase front: beside it, the DEVICE address of the ids' text-match values (KwQueryDev::wild_tm)
 
     // one or_iterator per token that exists in some field (kw_translate.h), in query order; returns the bytes of its lists
     uint64_t add_token(uint32_t i, QueryTokens& T, const KwTokenLists& tl, uint32_t len) {
@@ -749,7 +775,7 @@ struct BatchPlanner {
                 if (!in.excluded_ids) { P.status[i] = TSGPU_ERR_INVALID; return; }
                 A.aux.insert(A.aux.end(), in.excluded_ids, in.excluded_ids + in.n_excluded);
             }
-            if (wild_ids_dev && wild_ids_dev[i]) q.wild_ids = wild_ids_dev[i];      // (in.filter_ids is not a host address then)
+            if (wild_ids_dev && wild_ids_dev[i]) { q.wild_ids = wild_ids_dev[i]; if (wild_tm_dev) q.wild_tm = wild_tm_dev[i]; }      // (in.filter_ids is not a host address then)
             else if (in.n_filter) A.aux.insert(A.aux.end(), in.filter_ids, in.filter_ids + in.n_filter);
         }
         uint32_t n_ids = in.n_filter ? in.n_filter : ctx->num_docs;
@@ -1004,7 +1030,7 @@ struct BatchPlanner {
 }  // namespace
 
 static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query* queries, uint32_t n_queries, Plan& P, bool keep_ids, bool wildcard, const KwVFlat* vflat = nullptr,
-                      const uint16_t* present_elsewhere = nullptr, const uint64_t* wild_ids_dev = nullptr) {
+                      const uint16_t* present_elsewhere = nullptr, const uint64_t* wild_ids_dev = nullptr, const uint64_t* wild_tm_dev = nullptr) {
     static const bool plan_timing = getenv("TSGPU_HOST_TIMING") != nullptr;
     const uint64_t tp0 = now_us();
     P.q.resize(n_queries);
@@ -1012,7 +1038,7 @@ static int plan_batch(tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query
     P.cutoff.assign(n_queries, 0);
     BatchPlanner B{ctx, snap, queries, n_queries, P, keep_ids, wildcard, vflat, present_elsewhere, tp0,
                    std::vector<QueryCut>(n_queries), std::vector<uint32_t>(n_queries, 0), std::vector<uint32_t>(n_queries, 0), std::vector<double>(n_queries, 0.0), {}};
-    B.wild_ids_dev = wild_ids_dev;
+    B.wild_ids_dev = wild_ids_dev; B.wild_tm_dev = wild_tm_dev;
     const uint32_t min_par = ctx->plan_parallel_min_queries;
     const uint32_t min_slice = std::max<uint32_t>(8, min_par / 8);                      // (256 queries per slice at the default threshold)
     QuerySlices sl{n_queries, 1, 1};
@@ -1185,6 +1211,7 @@ struct BatchOpts {
     const uint16_t* present_elsewhere = nullptr;      // doc-range shard of a group whose members' dictionaries differ: per query, the tokens that exist on ANOTHER shard
                                                       // (missing here they are empty lists, not dropped tokens: kw_search_batch_masked, tsgpu_host.h); host planner
     const uint64_t* wild_ids_dev = nullptr;           // wildcard batch of the infix front (tsgpu_infix_search_batch): the queries' filter ids are device arrays (KwQueryDev::wild_ids)
+    const uint64_t* wild_tm_dev = nullptr;            // ... of the phrase front (tsgpu_phrase_search_batch): their text-match values, device arrays too (KwQueryDev::wild_tm)
 };
 }
 static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* queries, uint32_t n_queries, tsgpu_hits* out, const BatchOpts& bo);
@@ -1515,7 +1542,8 @@ struct HitTables {
     TablePlan tp[4]; size_t n[5], first[6] = {0}; uint64_t records = 0;      // (first: a table's place in the concatenation; first[5] = all work items)
     std::vector<uint32_t> oc_jobs[2];                                        // queries of the two multi-field tables that kw_mf_ordered_count_kernel counts
 };
-int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP, HitTables& H) {
+// force_two (the phrase front: its mark kernel needs the records): the two-kernel form whatever the number of hit-buffer groups
+int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP, HitTables& H, bool force_two = false) {
     for (int tb = 0; tb < 5; tb++) { H.n[tb] = DP.on && tb < 2 ? DP.n_work[tb] : P.n_tab[tb]; H.first[tb + 1] = H.first[tb] + H.n[tb]; }
     for (int tb = 0; tb < 4; tb++) {
         if (!H.n[tb] || !ctx->kw_two_kernels) continue;
@@ -1527,7 +1555,8 @@ int plan_hit_tables(const tsgpu_ctx* ctx, KwLane& L, Plan& P, const DevPlan& DP,
             if (int rc = L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) return rc;
         } else {
             tp = group_hit_segments(P.work.data() + H.first[tb], H.n[tb], rec_bytes, hit_budget_records(ctx, rec_bytes));
-            if (tp.two && L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) { (void)hipGetLastError(); tp.two = false; }      // no room for the hit buffer: the fused kernel needs none
+            if (force_two) { tp.two = true; if (int rc = L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) return rc; }
+            else if (tp.two && L.d_hits.reserve(std::max<uint64_t>(tp.need, 1) * rec_bytes)) { (void)hipGetLastError(); tp.two = false; }      // no room for the hit buffer: the fused kernel needs none
             if (!tp.two) tp.hoff.clear();
         }
         H.records += tp.records;
@@ -1664,7 +1693,7 @@ struct KwResultImage {
 // ---- launch: the index view of the batch, then find / score (or fused) kernels per table, wildcard scans, merge groups, merge ----
 struct LaunchStats { uint32_t hit_groups = 0; bool find_marked = false; };
 int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap, const Plan& P, const HitTables& H, const KwStaged& T, int cap, uint32_t n_queries,
-                 bool timing, bool count_touched, bool vflat, LaunchStats& st) {
+                 bool timing, bool count_touched, bool vflat, LaunchStats& st, const PhraseMarkArgs* phrase = nullptr) {
     int rc;
     IndexView v = make_view(ctx, snap);
     v.mf = T.mf;
@@ -1688,6 +1717,7 @@ int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap,
     }
     const KwQueryDev* dq = T.dq; const KwWorkItem* dw = T.dw; const uint32_t* daux = T.daux; uint32_t* ids_out = T.ids_out;
     if (timing) TSGPU_HIP_TRY(hipEventRecord(L.ev[0], s));
+    bool phrase_fused = false;
     auto run_table = [&](int tb, auto tmax_tag, auto mf_tag) {
         constexpr int TM = decltype(tmax_tag)::value;
         constexpr bool MFT = decltype(mf_tag)::value;
@@ -1707,21 +1737,26 @@ int launch_batch(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap,
                     }
                     const int mf_pipe = !ctx->kw_mf_pipelined ? 0 : (P.mf_max_fields <= 2 ? 2 : (P.mf_max_fields <= 4 ? 4 : 0));
                     if (mf_pipe) ctx->kw_mf_pipelined_launches++;
-                    launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, oc, !P.any_aux && !P.any_array, mf_pipe, P.any_vq);
+                    launch_find_score_mf<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, oc, !P.any_aux && !P.any_array, mf_pipe, P.any_vq, phrase);
                 }
                 else {
                     const bool mark = !st.find_marked;
                     st.find_marked = true;
-                    launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux, P.any_vq);
+                    launch_find_score<TM>(cap, s, (uint32_t)(b - a), v, dq, dw + first + a, shifted(T.part, first + a), daux, ids_out, P.any_s2, L.d_hits.as<uint32_t>(), T.hoff[tb] + a, mark && timing ? L.ev[3] : nullptr, ctx->kw_pair_blocks, !P.any_aux, P.any_vq, phrase);
                 }
             }
-        } else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_vq);
+        } else if (phrase) phrase_fused = true;             // (cannot happen: plan_hit_tables(force_two))
+        else if constexpr (MFT) launch_search_mf_cap<TM>(cap, s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_vq);
         else with_cap(cap, [&](auto c) { launch_search<TM, decltype(c)::value>(s, (uint32_t)nws, v, dq, dw + first, shifted(T.part, first), daux, ids_out, P.any_s2, P.any_vq); });
     };
     run_table(0, std::integral_constant<int, 3>(), std::false_type());
     run_table(1, std::integral_constant<int, KW_MAX_TOKENS>(), std::false_type());
     run_table(2, std::integral_constant<int, 3>(), std::true_type());
     run_table(3, std::integral_constant<int, KW_MAX_TOKENS>(), std::true_type());
+    if (phrase) {                                // the phrase front's find + mark launches: no partial lists, nothing to merge
+        TSGPU_HIP_TRY(hipGetLastError());
+        return phrase_fused ? fail(TSGPU_ERR_DEVICE, "tsgpu_phrase_search_batch: a table of AND items without hit records") : TSGPU_OK;
+    }
     const size_t sh = H.first[4];
     if (H.n[4] && P.any_vq) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value, true>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
     else if (H.n[4]) with_cap(cap, [&](auto c) { hipLaunchKernelGGL((kw_wildcard_kernel<decltype(c)::value>), dim3((uint32_t)H.n[4]), dim3(KW_THREADS), 0, s, v, dq, dw + sh, shifted(T.part, sh), daux, ids_out); });
@@ -1906,7 +1941,7 @@ static int kw_batch_on_lane(tsgpu_ctx* ctx, KwLane& L, const tsgpu_kw_query* que
             if (DP.on) ctx->kw_device_plans.fetch_add(1); else ctx->kw_device_plan_fallbacks.fetch_add(1);
             if (DP.on && keep_ids) P.ids_total = (DP.hit_blocks[0] + DP.hit_blocks[1]) * (uint64_t)BLOCK_IDS;
         }
-        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, bo.wildcard, bo.vflat, bo.present_elsewhere, bo.wild_ids_dev))) return rc;
+        if (!DP.on && (rc = plan_batch(ctx, snap, queries, n_queries, P, keep_ids, bo.wildcard, bo.vflat, bo.present_elsewhere, bo.wild_ids_dev, bo.wild_tm_dev))) return rc;
         const uint64_t t_planned = now_us();
         if (out->k_stride < P.max_k) return fail(TSGPU_ERR_INVALID, "tsgpu_keyword_search_batch: k_stride smaller than the largest topster_size");
         const uint32_t KS = out->k_stride;
@@ -2513,14 +2548,15 @@ const uint32_t INFIX_ROUND_MAX_QUERIES = 32768;            // (grid.y of the bit
 struct IndexViewLists { const ListDesc* lists; const BlockIds* blk_ids; const uint32_t* ids_payload; };     // what the union reads of a snapshot
 
 // the wildcard machinery over id lists that are on the device already: query j ranks the n_filter ids at wild[j]
-int infix_rank(tsgpu_ctx* ctx, const tsgpu_kw_query* q, uint32_t m, tsgpu_hits* out, const uint64_t* wild) {
+// (tm: the phrase front's text-match arrays beside them, KwQueryDev::wild_tm; nullptr = the constant 100)
+int infix_rank(tsgpu_ctx* ctx, const tsgpu_kw_query* q, uint32_t m, tsgpu_hits* out, const uint64_t* wild, const uint64_t* tm = nullptr) {
     struct CallerCount { std::atomic<int>& c; explicit CallerCount(std::atomic<int>& x) : c(x) { c.fetch_add(1); } ~CallerCount() { c.fetch_sub(1); } } cc(ctx->kw_callers);
     CtxMuForVectorKeys vq_hold;
     if (ctx->sort_keys_live.load(std::memory_order_relaxed) != 0 && names_vector_query_key(q, m)) vq_hold.take(ctx);
     BatchOpts bo;
     bo.wildcard = true;
     bo.record_last = false;
-    bo.wild_ids_dev = wild;
+    bo.wild_ids_dev = wild; bo.wild_tm_dev = tm;
     LaneLock ll(ctx, tsgpu::tls_avoid_lane0() ? -2 : -1);
     vq_hold.stream = ll.L->stream;
     return kw_batch_on_lane(ctx, *ll.L, q, m, out, bo);
@@ -2774,6 +2810,351 @@ extern "C" int tsgpu_infix_search_batch(tsgpu_ctx* ctx, const tsgpu_infix_query*
             if (const int rc = infix_batch(ctx, queries, n_queries, out, n_tokens_matched, n_infix_ids, lists.get())) return rc;
         }
     } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_infix_search_batch: host allocation failed"); }
+    if (ids_out) *ids_out = lists.release();
+    return ok();
+}
+
+// ---------------------------------------------------------------- phrase search (kw_phrase.hip.h)
+namespace {
+enum PhraseBuf { PB_UBITS, PB_FBITS, PB_QBITS, PB_XBITS, PB_FOUND, PB_FIELDS, PB_PAIR_FIRST, PB_NACC, PB_CLIST, PB_PAIR_OFF, PB_PAIR_NIDS, PB_CHUNK_P, PB_CHUNK_A, PB_CHUNK_B,
+                 PB_ITEMS, PB_UNIT_OF, PB_AUX, PB_SEGS, PB_FSLOT, PB_IDS, PB_TM, PB_OFF, PB_NIDS };
+const uint32_t PHRASE_ROUND_MAX_QUERIES = 8192;            // (pairs = queries x fields are grid.y of the bitmap kernels)
+
+// the intersections of the round's multi-token phrases: the AND items through the keyword planner (plan_batch: probe order, the cut into work items, the
+// hit-buffer groups) and its find kernels, kw_phrase_mark_kernel behind each find launch instead of the score kernel. Runs on the held lane's stream.
+int phrase_find_mark(tsgpu_ctx* ctx, KwLane& L, hipStream_t s, const Snapshot& snap, const tsgpu_kw_query* kq, uint32_t m, const PhraseMarkArgs& pa) {
+    Plan P; DevPlan DP;
+    int rc;
+    if ((rc = plan_batch(ctx, snap, kq, m, P, false, false))) return rc;
+    for (uint32_t i = 0; i < m; i++) if (P.status[i] != TSGPU_OK) return fail(P.status[i], "tsgpu_phrase_search_batch: the planner refused an AND item");
+    P.aux.push_back(0);
+    HitTables H;
+    if ((rc = plan_hit_tables(ctx, L, P, DP, H, true))) return rc;
+    KwStaged T;
+    if ((rc = upload_plan_image(L, s, P, DP, H, T))) return rc;
+    if ((rc = reserve_partials(L, (size_t)std::max<size_t>(H.first[5], 1) + P.groups.size(), 1, T.part))) return rc;
+    LaunchStats st;
+    return launch_batch(ctx, L, s, snap, P, H, T, 512, m, false, false, false, st, &pa);
+}
+
+// the hits of ranked queries kq[j] (query q_of[j] of the call) into the caller's arrays
+int phrase_rank(tsgpu_ctx* ctx, std::vector<tsgpu_kw_query>& kq, const std::vector<uint64_t>& wild, const std::vector<uint64_t>& tmv, const std::vector<uint32_t>& q_of,
+                uint32_t n_queries, tsgpu_hits* out) {
+    const uint32_t m = (uint32_t)kq.size();
+    int rc;
+    if (m == 0) return TSGPU_OK;
+    if (m == n_queries) return infix_rank(ctx, kq.data(), m, out, wild.data(), tmv.data());       // every query of the call, in order: straight into the caller's arrays
+    const size_t ks = out->k_stride;
+    std::vector<uint64_t> keys(m * ks), nm(m);
+    std::vector<int64_t> scores(m * ks * 3), tm(m * ks);
+    std::vector<float> vd(m * ks);
+    std::vector<int8_t> msi(m * ks);
+    std::vector<uint32_t> nh(m);
+    std::vector<int32_t> st(m), co(m);
+    tsgpu_hits tmp{TSGPU_MEM_HOST, out->k_stride, keys.data(), scores.data(), tm.data(), vd.data(), msi.data(), nh.data(), nm.data(), st.data(), co.data()};
+    if ((rc = infix_rank(ctx, kq.data(), m, &tmp, wild.data(), tmv.data()))) return rc;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint32_t i = q_of[j];
+        const size_t n = std::min<size_t>(nh[j], ks);
+        std::copy(keys.begin() + j * ks, keys.begin() + j * ks + n, out->keys + i * ks);
+        std::copy(scores.begin() + j * ks * 3, scores.begin() + (j * ks + n) * 3, out->scores + i * ks * 3);
+        if (out->text_match) std::copy(tm.begin() + j * ks, tm.begin() + j * ks + n, out->text_match + i * ks);
+        if (out->vector_distance) std::copy(vd.begin() + j * ks, vd.begin() + j * ks + n, out->vector_distance + i * ks);
+        if (out->match_score_index) std::copy(msi.begin() + j * ks, msi.begin() + j * ks + n, out->match_score_index + i * ks);
+        out->n_hits[i] = nh[j]; out->status[i] = st[j];
+        if (out->num_matched) out->num_matched[i] = nm[j];
+        if (out->search_cutoff) out->search_cutoff[i] = co[j];
+    }
+    return TSGPU_OK;
+}
+
+int phrase_batch(tsgpu_ctx* ctx, const tsgpu_phrase_query* queries, uint32_t n_queries, tsgpu_hits* out, std::vector<int32_t>& status, uint64_t* n_phrase_ids, tsgpu_id_lists* lists) {
+    for (uint32_t i = 0; i < n_queries; i++) {
+        status[i] = TSGPU_OK;
+        if (out) {
+            out->n_hits[i] = 0;
+            if (out->num_matched) out->num_matched[i] = 0;
+            if (out->search_cutoff) out->search_cutoff[i] = 0;
+        }
+        if (n_phrase_ids) n_phrase_ids[i] = 0;
+    }
+    std::lock_guard<std::mutex> lk(ctx->phrase_mu);            // one front at a time: it owns the scratch below
+    (void)hipSetDevice(ctx->device);
+    DevBuf* B = ctx->phrase_buf;
+    const std::shared_ptr<const Snapshot> sn = ctx->snapshot();
+    const uint64_t now = now_us();
+    const bool timing = ctx->phrase_timing;
+    const uint32_t cut = ctx->phrase_weight_cut;
+    int rc;
+
+    // ---- the queries' own checks
+    std::vector<uint32_t> active;
+    for (uint32_t i = 0; i < n_queries; i++) {
+        const tsgpu_phrase_query& q = queries[i];
+        int st = TSGPU_OK;
+        if (q.mode > TSGPU_PHRASE_EXCLUDE || q.n_fields == 0 || q.n_fields > TSGPU_MAX_PHRASE_FIELDS || q.n_sort > TSGPU_MAX_SORT_KEYS) st = TSGPU_ERR_INVALID;
+        else if (q.mode != TSGPU_PHRASE_EXCLUDE && ((q.n_filter && !q.filter_ids) || (q.n_excluded && !q.excluded_ids))) st = TSGPU_ERR_INVALID;
+        for (uint32_t f = 0; st == TSGPU_OK && f < q.n_fields; f++) if (sn->field_is_array.find(q.field_ids[f]) == sn->field_is_array.end()) st = TSGPU_ERR_INVALID;
+        for (uint32_t f = 0; st == TSGPU_OK && f < q.n_fields; f++) {
+            if (q.n_phrases[f] > TSGPU_MAX_PHRASES) { st = TSGPU_ERR_UNSUPPORTED; break; }
+            for (uint32_t p = 0; p < q.n_phrases[f]; p++) {
+                if (q.phrases[f][p].n_tokens == 0) { st = TSGPU_ERR_INVALID; break; }
+                if (q.phrases[f][p].n_tokens > TSGPU_MAX_QUERY_TOKENS) st = TSGPU_ERR_UNSUPPORTED;
+            }
+        }
+        if (st == TSGPU_OK && q.mode == TSGPU_PHRASE_RANK) st = check_sort_slots(ctx, q.sort, q.n_sort, false, false, nullptr);
+        if (st == TSGPU_OK && q.deadline_us != 0 && now > q.deadline_us) { st = TSGPU_ERR_DEADLINE; if (out && out->search_cutoff) out->search_cutoff[i] = 1; }
+        status[i] = st;
+        if (st == TSGPU_OK) active.push_back(i);
+    }
+
+    // ---- per query: its (field, phrase) units — a phrase with a token that has no posting list has none (:5950-5953) — and an upper bound of its id list
+    struct Unit { uint32_t T; uint32_t field; uint32_t h[TSGPU_MAX_QUERY_TOKENS]; const tsgpu_phrase* ph; };
+    const uint32_t num_docs = sn->num_docs;
+    const uint64_t words = ((uint64_t)num_docs + 31) / 32;
+    std::vector<std::vector<Unit>> units_of(n_queries);
+    std::vector<std::vector<uint32_t>> units_per_field(n_queries);        // [field] -> units of that field (in phrase order, contiguous in units_of)
+    std::vector<uint64_t> cap_of(n_queries, 0);
+    for (uint32_t i : active) {
+        const tsgpu_phrase_query& q = queries[i];
+        units_per_field[i].assign(q.n_fields, 0);
+        uint64_t sum = 0;
+        for (uint32_t f = 0; f < q.n_fields; f++)
+            for (uint32_t p = 0; p < q.n_phrases[f]; p++) {
+                const tsgpu_phrase& ph = q.phrases[f][p];
+                Unit u; u.T = ph.n_tokens; u.field = q.field_ids[f]; u.ph = &ph;
+                bool all = true;
+                uint64_t shortest = ~0ull;
+                for (uint32_t t = 0; t < ph.n_tokens && all; t++) {
+                    u.h[t] = sn->find_handle(q.field_ids[f], ph.term_ids[t]);
+                    all = u.h[t] != 0xFFFFFFFFu && sn->h_lists[u.h[t]].n_blocks != 0;
+                    if (all) shortest = std::min<uint64_t>(shortest, sn->h_lists[u.h[t]].n_ids);
+                }
+                if (!all) continue;
+                units_of[i].push_back(u); units_per_field[i][f]++;
+                sum += shortest;
+            }
+        cap_of[i] = std::min<uint64_t>(sum, words * 32);
+    }
+    if (words == 0) active.clear();                          // (no documents: nothing matches, status 0)
+
+    std::vector<std::vector<uint32_t>> ids_host(lists ? n_queries : 0);
+    const IndexViewLists ivl{sn->lists.as<ListDesc>(), sn->ar ? sn->ar->blk_ids.as<BlockIds>() : nullptr, sn->ar ? sn->ar->ids_payload.as<uint32_t>() : nullptr};
+    const uint32_t n_chunks = (uint32_t)((words + INFIX_EXPAND_WORDS - 1) / INFIX_EXPAND_WORDS);
+    for (size_t a0 = 0; a0 < active.size();) {
+        // ---- the round: the queries whose scratch fits
+        size_t a1 = a0;
+        uint64_t bytes = 0;
+        while (a1 < active.size() && a1 - a0 < PHRASE_ROUND_MAX_QUERIES) {
+            const uint32_t i = active[a1];
+            const tsgpu_phrase_query& q = queries[i];
+            const uint64_t n_pairs_q = q.mode == TSGPU_PHRASE_EXCLUDE ? 1 : q.n_fields;
+            const uint64_t need = words * 4 * (units_of[i].size() + n_pairs_q + 1 + (q.mode != TSGPU_PHRASE_EXCLUDE && q.filter_ids ? 1 : 0)) + n_pairs_q * cut * 4ull + cap_of[i] * 12;
+            if (a1 > a0 && bytes + need > ctx->phrase_round_max_bytes) break;
+            bytes += need; a1++;
+        }
+        const uint32_t nr = (uint32_t)(a1 - a0);
+        ctx->phrase_rounds.fetch_add(1);
+        std::vector<PhraseFieldDev> pairs;
+        std::vector<uint32_t> pair_first(nr + 1, 0), unit_of_item, aux, fslot(nr, INFIX_NO_POS);
+        std::vector<tsgpu_kw_query> and_items;
+        std::vector<InfixMarkItem> mark_items;
+        std::vector<InfixIdSeg> segs_f, segs_x;
+        std::vector<uint64_t> off_cap, caps;
+        uint32_t n_units = 0, nf = 0;
+        uint64_t ids_total = 0;
+        bool any_rank = false;
+        for (uint32_t slot = 0; slot < nr; slot++) {
+            const uint32_t i = active[a0 + slot];
+            const tsgpu_phrase_query& q = queries[i];
+            const bool excl = q.mode == TSGPU_PHRASE_EXCLUDE;
+            any_rank = any_rank || q.mode == TSGPU_PHRASE_RANK;
+            pair_first[slot] = (uint32_t)pairs.size();
+            if (excl) pairs.push_back(PhraseFieldDev{n_units, (uint32_t)units_of[i].size(), q.mode, 0});
+            else {
+                uint32_t first = n_units;
+                for (uint32_t f = 0; f < q.n_fields; f++) { pairs.push_back(PhraseFieldDev{first, units_per_field[i][f], q.mode, q.field_weights[f]}); first += units_per_field[i][f]; }
+            }
+            for (const Unit& u : units_of[i]) {
+                const uint32_t unit = n_units++;
+                if (u.T == 1) {                                // get_phrase_matches passes every id of the list (:1796-1800)
+                    const uint32_t nb = sn->h_lists[u.h[0]].n_blocks;
+                    for (uint32_t b = 0; b < nb; b += INFIX_MARK_BLOCKS) mark_items.push_back(InfixMarkItem{unit, u.h[0], b, std::min(nb, b + INFIX_MARK_BLOCKS)});
+                } else {
+                    tsgpu_kw_query k;
+                    memset(&k, 0, sizeof k);
+                    k.n_tokens = u.T;
+                    for (uint32_t t = 0; t < u.T; t++) k.term_ids[t] = u.ph->term_ids[t];
+                    k.n_fields = 1; k.field_ids[0] = u.field;
+                    k.topster_size = 1;
+                    and_items.push_back(k); unit_of_item.push_back(unit);
+                }
+            }
+            if (!excl && q.filter_ids) {
+                fslot[slot] = nf;
+                if (q.n_filter) { segs_f.push_back(InfixIdSeg{aux.size(), q.n_filter, nf}); aux.insert(aux.end(), q.filter_ids, q.filter_ids + q.n_filter); }
+                nf++;
+            }
+            if (!excl && q.n_excluded) { segs_x.push_back(InfixIdSeg{aux.size(), q.n_excluded, slot}); aux.insert(aux.end(), q.excluded_ids, q.excluded_ids + q.n_excluded); }
+            off_cap.push_back(ids_total); caps.push_back(cap_of[i]);
+            ids_total += cap_of[i];
+        }
+        const uint32_t n_pairs = (uint32_t)pairs.size();
+        pair_first[nr] = n_pairs;
+        off_cap.insert(off_cap.end(), caps.begin(), caps.end());
+        std::vector<uint64_t> pair_off_cap(2 * (size_t)n_pairs);
+        for (uint32_t p = 0; p < n_pairs; p++) { pair_off_cap[p] = (uint64_t)p * cut; pair_off_cap[n_pairs + p] = cut; }
+        std::vector<InfixIdSeg> segs(segs_f);
+        segs.insert(segs.end(), segs_x.begin(), segs_x.end());
+        ctx->phrase_items.fetch_add(n_units);
+        if (!and_items.empty() && !ctx->kw_two_kernels) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_phrase_search_batch: needs the two-kernel keyword form (option kw_two_kernels)");
+
+        // ---- the device side of the round, on the stream of one lane held until the front's sync (the find kernels use the lane's tables and hit buffer)
+        std::vector<uint32_t> nids(nr), chunk_a((size_t)nr * n_chunks);
+        unsigned long long stats[2] = {0, 0};
+        {
+            LaneLock ll(ctx, tsgpu::tls_avoid_lane0() ? -2 : -1);
+            KwLane& L = *ll.L;
+            hipStream_t s = L.stream;
+            const size_t nu = std::max<uint32_t>(n_units, 1);
+            if ((rc = B[PB_UBITS].reserve(nu * words * 4)) || (rc = B[PB_FBITS].reserve((size_t)n_pairs * words * 4)) || (rc = B[PB_QBITS].reserve((size_t)nr * words * 4)) ||
+                (rc = B[PB_XBITS].reserve((size_t)std::max<uint32_t>(nf, 1) * words * 4)) || (rc = B[PB_FOUND].reserve((nu + 2) * 8)) ||
+                (rc = upload(B[PB_FIELDS], pairs.data(), pairs.size() * sizeof(PhraseFieldDev), s)) || (rc = upload(B[PB_PAIR_FIRST], pair_first.data(), pair_first.size() * 4, s)) ||
+                (rc = B[PB_NACC].reserve((size_t)n_pairs * 4)) || (rc = B[PB_CLIST].reserve((size_t)n_pairs * cut * 4)) ||
+                (rc = upload(B[PB_PAIR_OFF], pair_off_cap.data(), pair_off_cap.size() * 8, s)) || (rc = B[PB_PAIR_NIDS].reserve((size_t)n_pairs * 4)) ||
+                (rc = B[PB_CHUNK_P].reserve((size_t)n_pairs * n_chunks * 4)) || (rc = B[PB_CHUNK_A].reserve((size_t)nr * n_chunks * 4)) || (rc = B[PB_CHUNK_B].reserve((size_t)nr * n_chunks * 4)) ||
+                (rc = upload(B[PB_ITEMS], mark_items.data(), mark_items.size() * sizeof(InfixMarkItem), s)) || (rc = upload(B[PB_UNIT_OF], unit_of_item.data(), unit_of_item.size() * 4, s)) ||
+                (rc = upload(B[PB_AUX], aux.data(), aux.size() * 4, s)) || (rc = upload(B[PB_SEGS], segs.data(), segs.size() * sizeof(InfixIdSeg), s)) ||
+                (rc = upload(B[PB_FSLOT], fslot.data(), fslot.size() * 4, s)) || (rc = upload(B[PB_OFF], off_cap.data(), off_cap.size() * 8, s)) ||
+                (rc = B[PB_IDS].reserve((size_t)std::max<uint64_t>(ids_total, 1) * 4)) || (rc = B[PB_TM].reserve((size_t)std::max<uint64_t>(ids_total, 1) * 8)) ||
+                (rc = B[PB_NIDS].reserve((size_t)nr * 4))) return rc;
+            TSGPU_HIP_TRY(hipMemsetAsync(B[PB_UBITS].p, 0, nu * words * 4, s));
+            TSGPU_HIP_TRY(hipMemsetAsync(B[PB_FBITS].p, 0, (size_t)n_pairs * words * 4, s));
+            TSGPU_HIP_TRY(hipMemsetAsync(B[PB_FOUND].p, 0, (nu + 2) * 8, s));
+            if (nf) TSGPU_HIP_TRY(hipMemsetAsync(B[PB_XBITS].p, 0, (size_t)nf * words * 4, s));
+            uint32_t* ubits = B[PB_UBITS].as<uint32_t>();
+            uint32_t* fbits = B[PB_FBITS].as<uint32_t>();
+            uint32_t* qbits = B[PB_QBITS].as<uint32_t>();
+            unsigned long long* found = B[PB_FOUND].as<unsigned long long>();
+            uint64_t t_ph = 0;
+            if (timing) { TSGPU_HIP_TRY(hipStreamSynchronize(s)); t_ph = now_us(); }
+            if (!and_items.empty()) {
+                const PhraseMarkArgs pa{B[PB_UNIT_OF].as<uint32_t>(), ubits, words, found, found + nu};
+                if ((rc = phrase_find_mark(ctx, L, s, *sn, and_items.data(), (uint32_t)and_items.size(), pa))) { (void)hipStreamSynchronize(s); return rc; }
+            }
+            if (!mark_items.empty())
+                hipLaunchKernelGGL(infix_union_mark_kernel, dim3((uint32_t)mark_items.size()), dim3(INFIX_THREADS), 0, s, B[PB_ITEMS].as<InfixMarkItem>(), ivl.lists, ivl.blk_ids, ivl.ids_payload,
+                                   ubits, words, found);
+            if (timing) { TSGPU_HIP_TRY(hipStreamSynchronize(s)); const uint64_t t = now_us(); ctx->phrase_mark_us.fetch_add(t - t_ph); t_ph = t; }
+            hipLaunchKernelGGL(phrase_fold_kernel, dim3(n_pairs), dim3(PHRASE_THREADS), 0, s, B[PB_FIELDS].as<PhraseFieldDev>(), ubits, found, fbits, words, B[PB_NACC].as<uint32_t>());
+            if (any_rank) {                                    // the first `cut` ids of every folded field: the ids that get the field's weight score
+                hipLaunchKernelGGL(infix_count_kernel, dim3(n_chunks, n_pairs), dim3(INFIX_THREADS), 0, s, fbits, words, B[PB_CHUNK_P].as<uint32_t>());
+                hipLaunchKernelGGL(infix_expand_kernel, dim3(n_chunks, n_pairs), dim3(INFIX_THREADS), 0, s, fbits, words, B[PB_CHUNK_P].as<uint32_t>(), B[PB_CLIST].as<uint32_t>(),
+                                   B[PB_PAIR_OFF].as<uint64_t>(), B[PB_PAIR_OFF].as<uint64_t>() + n_pairs, B[PB_PAIR_NIDS].as<uint32_t>());
+            }
+            hipLaunchKernelGGL(phrase_or_fields_kernel, dim3((uint32_t)((words + PHRASE_THREADS - 1) / PHRASE_THREADS), nr), dim3(PHRASE_THREADS), 0, s, fbits, B[PB_PAIR_FIRST].as<uint32_t>(), qbits, words);
+            if (!segs_x.empty())
+                hipLaunchKernelGGL(infix_idlist_clear_kernel, dim3((uint32_t)segs_x.size(), 8), dim3(INFIX_THREADS), 0, s, B[PB_AUX].as<uint32_t>(), B[PB_SEGS].as<InfixIdSeg>() + segs_f.size(), qbits, words);
+            hipLaunchKernelGGL(infix_count_kernel, dim3(n_chunks, nr), dim3(INFIX_THREADS), 0, s, qbits, words, B[PB_CHUNK_A].as<uint32_t>());      // after exclusion, before the filter: n_phrase_ids
+            uint32_t* chunk_final = B[PB_CHUNK_A].as<uint32_t>();
+            if (nf) {
+                if (!segs_f.empty())
+                    hipLaunchKernelGGL(infix_idlist_set_kernel, dim3((uint32_t)segs_f.size(), 8), dim3(INFIX_THREADS), 0, s, B[PB_AUX].as<uint32_t>(), B[PB_SEGS].as<InfixIdSeg>(), B[PB_XBITS].as<uint32_t>(), words);
+                hipLaunchKernelGGL(infix_bits_and_kernel, dim3((uint32_t)((words + INFIX_THREADS - 1) / INFIX_THREADS), nr), dim3(INFIX_THREADS), 0, s, qbits, B[PB_XBITS].as<uint32_t>(),
+                                   B[PB_FSLOT].as<uint32_t>(), words);
+                chunk_final = B[PB_CHUNK_B].as<uint32_t>();
+                hipLaunchKernelGGL(infix_count_kernel, dim3(n_chunks, nr), dim3(INFIX_THREADS), 0, s, qbits, words, chunk_final);
+            }
+            hipLaunchKernelGGL(infix_expand_kernel, dim3(n_chunks, nr), dim3(INFIX_THREADS), 0, s, qbits, words, chunk_final, B[PB_IDS].as<uint32_t>(), B[PB_OFF].as<uint64_t>(),
+                               B[PB_OFF].as<uint64_t>() + nr, B[PB_NIDS].as<uint32_t>());
+            if (any_rank)
+                hipLaunchKernelGGL(phrase_tm_kernel, dim3(32, nr), dim3(PHRASE_THREADS), 0, s, B[PB_IDS].as<uint32_t>(), B[PB_OFF].as<uint64_t>(), B[PB_OFF].as<uint64_t>() + nr,
+                                   B[PB_NIDS].as<uint32_t>(), B[PB_PAIR_FIRST].as<uint32_t>(), B[PB_FIELDS].as<PhraseFieldDev>(), B[PB_NACC].as<uint32_t>(), B[PB_CLIST].as<uint32_t>(), cut,
+                                   B[PB_TM].as<int64_t>());
+            TSGPU_HIP_TRY(hipGetLastError());
+            TSGPU_HIP_TRY(hipMemcpyAsync(nids.data(), B[PB_NIDS].p, (size_t)nr * 4, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(chunk_a.data(), B[PB_CHUNK_A].p, (size_t)nr * n_chunks * 4, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipMemcpyAsync(stats, found + nu, 16, hipMemcpyDeviceToHost, s));
+            TSGPU_HIP_TRY(hipStreamSynchronize(s));
+            ctx->phrase_syncs.fetch_add(1);
+            if (timing) ctx->phrase_fold_us.fetch_add(now_us() - t_ph);
+            ctx->phrase_records_checked.fetch_add(stats[0]); ctx->phrase_records_matched.fetch_add(stats[1]);
+
+            // the surviving ids: to the caller's list object here; the ranked queries' stay on the device for the wildcard ranking below
+            bool copied = false;
+            for (uint32_t slot = 0; slot < nr; slot++) {
+                const uint32_t i = active[a0 + slot];
+                if (nids[slot] > caps[slot]) return fail(TSGPU_ERR_DEVICE, "tsgpu_phrase_search_batch: an id list beyond its bound");
+                uint64_t before_filter = 0;
+                for (uint32_t c = 0; c < n_chunks; c++) before_filter += chunk_a[(size_t)slot * n_chunks + c];
+                if (n_phrase_ids) n_phrase_ids[i] = before_filter;
+                if (lists && nids[slot]) {
+                    ids_host[i].resize(nids[slot]);
+                    TSGPU_HIP_TRY(hipMemcpyAsync(ids_host[i].data(), B[PB_IDS].as<uint32_t>() + off_cap[slot], (size_t)nids[slot] * 4, hipMemcpyDeviceToHost, s));
+                    copied = true;
+                }
+            }
+            if (lists) { if (copied) TSGPU_HIP_TRY(hipStreamSynchronize(s)); ctx->phrase_syncs.fetch_add(1); }
+        }
+
+        // ---- ranking (mode RANK): the id list and its text scores, both still on the device, through the wildcard machinery
+        std::vector<tsgpu_kw_query> kq;
+        std::vector<uint64_t> wild, tmv;
+        std::vector<uint32_t> q_of;
+        for (uint32_t slot = 0; slot < nr; slot++) {
+            const uint32_t i = active[a0 + slot];
+            const tsgpu_phrase_query& q = queries[i];
+            if (q.mode != TSGPU_PHRASE_RANK || nids[slot] == 0) continue;
+            const uint32_t* d_ids = B[PB_IDS].as<uint32_t>() + off_cap[slot];
+            tsgpu_kw_query k;
+            memset(&k, 0, sizeof k);
+            k.n_sort = q.n_sort;
+            for (uint32_t x = 0; x < q.n_sort; x++) k.sort[x] = q.sort[x];
+            k.topster_size = q.topster_size;
+            k.filter_ids = d_ids;                                  // (a device address: read through KwQueryDev::wild_ids only)
+            k.n_filter = nids[slot];
+            k.deadline_us = q.deadline_us;
+            kq.push_back(k); wild.push_back((uint64_t)(uintptr_t)d_ids); tmv.push_back((uint64_t)(uintptr_t)(B[PB_TM].as<int64_t>() + off_cap[slot])); q_of.push_back(i);
+        }
+        const uint64_t t_rank = timing ? now_us() : 0;
+        if (!kq.empty()) {
+            if (!out) return fail(TSGPU_ERR_INVALID, "tsgpu_phrase_search_batch: a RANK query needs out");
+            // (phrase_rank writes out->status of the ranked queries; the others keep theirs, copied to out by the caller)
+            if ((rc = phrase_rank(ctx, kq, wild, tmv, q_of, n_queries, out))) return rc;
+            for (uint32_t j = 0; j < (uint32_t)q_of.size(); j++) status[q_of[j]] = out->status[q_of[j]];
+        }
+        if (timing) ctx->phrase_rank_us.fetch_add(now_us() - t_rank);
+        a0 = a1;
+    }
+    if (lists) {
+        lists->begin.assign((size_t)n_queries + 1, 0);
+        for (uint32_t i = 0; i < n_queries; i++) { lists->ids.insert(lists->ids.end(), ids_host[i].begin(), ids_host[i].end()); lists->begin[i + 1] = lists->ids.size(); }
+    }
+    return TSGPU_OK;
+}
+}  // namespace
+
+extern "C" int tsgpu_phrase_search_batch(tsgpu_ctx* ctx, const tsgpu_phrase_query* queries, uint32_t n_queries, tsgpu_hits* out, uint64_t* n_phrase_ids, tsgpu_id_lists** ids_out) {
+    if (ids_out) *ids_out = nullptr;
+    if (!ctx) return fail(TSGPU_ERR_INVALID, "tsgpu_phrase_search_batch: NULL argument");
+    if (out && out->mem != TSGPU_MEM_HOST) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_phrase_search_batch: host outputs only");
+    if (ctx->doc_range_set) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_phrase_search_batch: not served on a doc-range shard");
+    std::unique_ptr<tsgpu_id_lists> lists;
+    if (ids_out) { lists.reset(new (std::nothrow) tsgpu_id_lists); if (!lists) return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_phrase_search_batch: host allocation failed"); }
+    try {
+        if (lists) lists->begin.assign((size_t)n_queries + 1, 0);
+        if (n_queries) {
+            if (!queries) return fail(TSGPU_ERR_INVALID, "tsgpu_phrase_search_batch: queries is NULL");
+            if (out && (!out->n_hits || !out->status)) return fail(TSGPU_ERR_INVALID, "tsgpu_phrase_search_batch: missing output arrays");
+            bool any_rank = false;
+            for (uint32_t i = 0; i < n_queries; i++) any_rank = any_rank || queries[i].mode == TSGPU_PHRASE_RANK;
+            if (any_rank && (!out || !out->keys || !out->scores)) return fail(TSGPU_ERR_INVALID, "tsgpu_phrase_search_batch: a RANK query needs the output arrays");
+            std::vector<int32_t> status(n_queries, TSGPU_OK);
+            if (const int rc = phrase_batch(ctx, queries, n_queries, out, status, n_phrase_ids, lists.get())) return rc;
+            if (out) for (uint32_t i = 0; i < n_queries; i++) out->status[i] = status[i];
+            else for (uint32_t i = 0; i < n_queries; i++) if (status[i] != TSGPU_OK) return fail(status[i], "tsgpu_phrase_search_batch: a query was refused (no out to report it in)");
+        }
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_phrase_search_batch: host allocation failed"); }
     if (ids_out) *ids_out = lists.release();
     return ok();
 }

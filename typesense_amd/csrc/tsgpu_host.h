@@ -665,6 +665,15 @@ struct tsgpu_ctx {
     tsgpu::DevBuf infix_buf[16];
     std::atomic<uint64_t> infix_scan_launches{0}, infix_tokens_scanned{0}, infix_tokens_matched{0}, infix_lists_marked{0}, infix_rounds{0};
 
+    // phrase search (tsgpu_phrase_search_batch; kw_phrase.hip.h): the front's scratch (one phrase batch at a time: phrase_mu; it runs on the stream of the lane it holds)
+    uint64_t phrase_round_max_bytes = 2ull << 30;    // option: bitmap + id-list scratch of one round of a batch
+    uint32_t phrase_weight_cut = 10000;              // option, TESTS ONLY: ids per field that get the field's weight score (src/index.cpp:5991)
+    bool phrase_timing = false;                      // option (measurement only): a stream sync behind every phase of the front, host wall clock per phase in the counters below
+    std::atomic<uint64_t> phrase_mark_us{0}, phrase_fold_us{0}, phrase_rank_us{0};
+    std::mutex phrase_mu;
+    tsgpu::DevBuf phrase_buf[24];
+    std::atomic<uint64_t> phrase_items{0}, phrase_records_checked{0}, phrase_records_matched{0}, phrase_rounds{0}, phrase_syncs{0};
+
     std::unordered_map<uint32_t, tsgpu::VecField*> vec_fields;
     std::unordered_map<uint32_t, tsgpu::FacetField*> facet_fields;
     tsgpu::GroupByScratch* groupby = nullptr;        // device scratch of tsgpu_keyword_search_grouped_batch (under mu)

@@ -106,6 +106,37 @@ class InfixQuery:
         c.deadline_us = self.deadline_us
 
 
+class PhraseQuery:
+    """One do_phrase_search / handle_exclusion call (src/index.cpp:5909-6086, :6274-6324): tsgpu_phrase_query. fields: [(field id, weight, [phrase, ...])] in
+    query_by order, a phrase = its term ids in order. filter_ids: None = no filter; an EMPTY array = a filter that matched nothing."""
+
+    def __init__(self, fields, mode=B.PHRASE_RANK, sort=((B.SORT_TEXT_MATCH, 1, 0), (B.SORT_SEQ_ID, 1, 0)), topster_size=0, excluded_ids=None, filter_ids=None, deadline_us=0):
+        self.fields = [(int(f), int(w), [list(p) for p in phrases]) for f, w, phrases in fields]
+        self.mode, self.sort, self.topster_size, self.deadline_us = mode, tuple(sort), topster_size, deadline_us
+        self.excluded_ids = None if excluded_ids is None else _u32(excluded_ids)
+        self.filter_ids = None if filter_ids is None else _u32(filter_ids)
+        self._empty = np.zeros(1, np.uint32)             # (what a filter without ids points at: non-NULL)
+
+    def fill(self, c):
+        c.mode, c.n_fields = self.mode, len(self.fields)
+        for f, (field, weight, phrases) in enumerate(self.fields[:B.MAX_PHRASE_FIELDS]):
+            c.field_ids[f], c.field_weights[f], c.n_phrases[f] = field, weight, len(phrases)
+            for p, toks in enumerate(phrases[:B.MAX_PHRASES]):
+                c.phrases[f][p].n_tokens = len(toks)
+                for t, term in enumerate(toks[:B.MAX_QUERY_TOKENS]):
+                    c.phrases[f][p].term_ids[t] = int(term)
+        c.n_sort = len(self.sort)
+        for i, s in enumerate(self.sort[:3]):
+            c.sort[i].kind, c.sort[i].order, c.sort[i].column = s
+        c.topster_size = self.topster_size
+        if self.excluded_ids is not None and self.excluded_ids.size:
+            c.excluded_ids, c.n_excluded = self.excluded_ids.ctypes.data, self.excluded_ids.size
+        if self.filter_ids is not None:
+            c.filter_ids = (self.filter_ids if self.filter_ids.size else self._empty).ctypes.data
+            c.n_filter = self.filter_ids.size
+        c.deadline_us = self.deadline_us
+
+
 class Hits:
     """Host copy of tsgpu_hits for a batch (numpy, [n_queries, k_stride, ...])."""
 
@@ -424,6 +455,30 @@ class GpuIndex:
             finally:
                 self.L.tsgpu_id_lists_free(lists)
         return hits, n_tok, n_ids, ids
+
+    # ---- phrase search (Index::do_phrase_search / handle_exclusion) ----
+    def phrase_search_batch(self, queries, k_stride=250, hits=None, want_ids=True, with_hits=True):
+        """list[PhraseQuery] -> (Hits (None without with_hits: no query may have mode RANK then), n_phrase_ids [n] u64, per query the surviving ids ascending
+        (None without want_ids))"""
+        n = len(queries)
+        arr = (B.PhraseQueryC * max(n, 1))()
+        for i, q in enumerate(queries):
+            q.fill(arr[i])
+        hits = (hits or Hits(n, k_stride)) if with_hits else None
+        hs = hits.c_struct() if with_hits else None
+        n_ids = np.zeros(n, np.uint64)
+        lists = C.c_void_p()
+        self._ck(self.L.tsgpu_phrase_search_batch(self.h, C.cast(arr, C.c_void_p), n, C.byref(hs) if with_hits else None, _vp(n_ids), C.byref(lists) if want_ids else None))
+        ids = None
+        if want_ids:
+            try:
+                ids = []
+                for q in range(n):
+                    cnt = self.L.tsgpu_id_lists_count(lists, q)
+                    ids.append(np.ctypeslib.as_array(self.L.tsgpu_id_lists_ids(lists, q), shape=(cnt,)).copy() if cnt else np.zeros(0, np.uint32))
+            finally:
+                self.L.tsgpu_id_lists_free(lists)
+        return hits, n_ids, ids
 
     # ---- facet counting over matched ids (do_facets, hash-index branch) ----
     def keyword_search_grouped_batch(self, queries, groups, k_stride, g_stride=250, want_ids=False, want_registers=False):
