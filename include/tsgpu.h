@@ -196,6 +196,7 @@ int tsgpu_set_option(tsgpu_ctx* ctx, const char* name, int64_t value);
 /* introspection counters (tests / bench): "vec_overflow_rounds", "vec_prefilter_groups", "vec_prefilter_fallbacks",
  * "vec_filter_direct_queries" / "vec_filter_scan_queries" (filtered queries of tsgpu_vec_knn_batch_filtered answered by either route),
  * "vec_search_pq_flat_queries" / "vec_search_pq_kcut_queries" / "vec_search_pq_flat_lists" / "vec_search_pq_flat_launches" (tsgpu_vector_search_batch_per_query, cumulative),
+ * "vec_grouped_flat_queries" / "vec_grouped_kcut_queries" / "vec_grouped_items" / "vec_grouped_syncs" / "vec_grouped_sync_us" (tsgpu_vector_search_grouped_batch, cumulative),
  * "vec_filter_h2d_bytes" (bytes of id lists uploaded for them), "vec_filter_stage_us" / "vec_filter_build_us" (host time staging and uploading the lists / time of the
  * bitmap and survivor-list build kernels; both kept under "vec_count_rescored"),
  * "vec_rescored_rows", "vec_candidate_rows" (rows of the last bracket group that reached the exact re-score / that passed the scan's tile-level bound),
@@ -819,6 +820,41 @@ int tsgpu_vector_search_batch_per_query(tsgpu_ctx* ctx, uint32_t vec_field_id, c
                                         const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out);
 int tsgpu_vector_search_batch_per_query_ids(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params /* [n_q] */,
                                             const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out, tsgpu_id_lists** ids_out);
+/* group_by for the pure vector search: the vector branch of Index::search with group_limit != 0 (src/index.cpp:3677-3723 — get_distinct_id per surviving id,
+ * topster->add(&kv) into the distinct Topster, groups_processed[distinct_id]++), both passes, one parameter block and one tsgpu_group_by per request.
+ * groups[i] is read as in tsgpu_keyword_search_grouped_batch (group_limit, column, first_pass, group_missing_values); its `wildcard` field is ignored.
+ *   Branch, k, query document, filter: exactly tsgpu_vector_search_batch_per_query's. A query is FLAT iff n_filter != 0 && n_filter < flat_search_cutoff (:3664);
+ *     k = k ? k : fetch_size (:3646), + 1 when the query document passes the functor (:3651-3654); the k-cut branch honours the excluded ids, the flat branch
+ *     does not consult them; the query document itself is left out (:3686); cosine distances go through std::abs and an id with vec_dist_score >
+ *     distance_threshold is dropped (:3699-3704); an id without a stored vector is skipped in the flat branch (:3355-3360).
+ *   The ITEMS of a query are the ids that survive those rules, each with its vec_dist_score: what is left of the k nearest (k-cut: at most 1 025 ids), or of
+ *     every filter id (flat).
+ *   The KV of an item: scores = sort_scores(..., text-match slot 0, vec_dist_score) (:3709-3711), vector_distance = vec_dist_score, distinct key read from
+ *     groups[i].column as the grouped keyword call reads it (an id beyond the column: 1 with group_missing_values, else its seq_id). Every sort kind the
+ *     per-query call serves is served.
+ *   Topster capacity: params[i].topster_size, else max(fetch_size, 250) capped by n_filter (by the collection size without a filter), :3506-3512; above
+ *     TSGPU_MAX_TOPK the query answers 501.
+ *   Passes and outputs are tsgpu_keyword_search_grouped_batch's: first_pass, the hit layout (group r at [r * group_limit, ...) in a second pass), n_groups,
+ *     distinct_key, group_size, group_found (the group's members among the items), groups_total, groups_count, loglog_registers, text_match and
+ *     match_score_index. num_matched[i] = the number of items; *ids_out (nullable) = per query the items' ids, ascending (nearest_ids, :3724-3732);
+ *     vector_distance = the hit's vec_dist_score.
+ * Per-query status (the neighbours of a failing query are answered; n_hits = 0, n_groups = 0, an empty id list): what tsgpu_vector_search_batch_per_query
+ * refuses is refused alike (400 / 501); group_limit outside 1..TSGPU_MAX_GROUP_LIMIT 400; an unknown group column 404; a sort kind this path does not serve
+ * (_group_found, kinds >= TSGPU_SORT_EVAL) 501; k_stride / g_stride too small for that query 400 — with B = min(capacity, item bound), the bound being k of a
+ * k-cut query and n_filter of a flat one, g_stride must hold B groups and k_stride B hits (first pass) or B * group_limit (second pass).
+ * Failures of the call: NULL arguments, an unknown field, out->mem != TSGPU_MEM_HOST (501), a context that is a doc-range shard (501).
+ * The call holds the index lock from the flat distances to the delivery, as the grouped keyword call does; it is safe with concurrent callers; calls are not
+ * coalesced. Device path: the k-cut queries run as ONE tsgpu_vec_knn_batch_filtered whose results the host finishes and uploads; the flat queries' ragged
+ * distance array stays on the device, where gb_vec_items_kernel compacts every segment into (seq_id, vec_dist_score) items in list order; the host downloads
+ * the per-query counts (one stream sync per batch that has flat queries) to size the group tables, then the gb_* kernels of the grouped keyword call run.
+ * Counters (cumulative): "vec_grouped_flat_queries", "vec_grouped_kcut_queries", "vec_grouped_items", "vec_grouped_syncs" ("vec_grouped_sync_us": host time
+ * waiting in those syncs, which covers the distance launches and the compaction queued before the download); the ragged launches count in
+ * "vec_search_pq_flat_launches", the distinct lists in "vec_search_pq_flat_lists".
+ * Not served: group_by under hybrid search; group_by under infix and phrase search (their id lists and text-match arrays are on the device already: the
+ * per-item value seam of this call is the one they will use); the tsgpu_group_* shard form; device-memory outputs; coalescing of one-query calls; HNSW as
+ * the k-cut engine; sort kinds >= TSGPU_SORT_EVAL. */
+int tsgpu_vector_search_grouped_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params /* [n_q] */, const tsgpu_group_by* groups /* [n_q] */,
+                                      const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out, tsgpu_grouped_hits* gout, tsgpu_id_lists** ids_out /* nullable */);
 
 /* ------------------------------------------------------------------ hybrid (B3) */
 typedef struct tsgpu_hybrid_params {

@@ -63,7 +63,7 @@ struct GbQuery {
     uint32_t first_block;     // the query's first workgroup in the per-item launches (ceil(n_items / GB_THREADS) workgroups each: no workgroup spans two queries)
     uint32_t first_sblock;    // ... and in the member scatter (ceil(n_items / GB_SCATTER_ITEMS) workgroups each)
     uint8_t first_pass, group_missing_values, wildcard, run;   // run = 0: the query failed upstream, nothing is produced
-    uint8_t iota, dedupe, forced, pad[5];   // forced: the groups to return are GIVEN (forced_begin / n_forced below). iota: q = * over the whole collection, the matched ids are 0 .. n_items - 1 (gb_iota_kernel writes them); dedupe: a SECOND pass over several
+    uint8_t iota, dedupe, forced, vec, pad[4];   // vec: a pure vector search (tsgpu_vector_search_grouped_batch): item i carries GbArgs::vd[i], the text-match slot is 0. forced: the groups to return are GIVEN (forced_begin / n_forced below). iota: q = * over the whole collection, the matched ids are 0 .. n_items - 1 (gb_iota_kernel writes them); dedupe: a SECOND pass over several
                               // candidate combinations — a document met by several of them counts once, with its greatest KV (the later combination on ties)
     uint32_t pw_begin, pw_cap;      // second pass: the query's chunk work list (entries [pw_begin, pw_begin + pw_cap): n_items / GB_CHUNK + n_items / GB_BIG + 1 at most)
     uint64_t pbuf_off;              // ... and its partial top-L buffer (pw_cap x group_limit entries)
@@ -87,6 +87,7 @@ struct GbArgs {
     int64_t* pb_s0; int64_t* pb_s1; int64_t* pb_s2; int64_t* pb_key;           // partial top-L lists (sorted), group_limit entries per work-list entry
     uint64_t n_items;
     const uint32_t* ids;                                                       // matched ids, ascending per query
+    const float* vd;                                                           // per matched id of a vector query (GbQuery::vec): its vec_dist_score
     int64_t* s0; int64_t* s1; int64_t* s2; unsigned long long* dkey; uint32_t* rslot;    // per matched id
     unsigned long long* hkey; uint32_t* hcount; uint32_t* hbest; uint32_t* hrank;          // per table slot
     uint32_t* glist; uint32_t* gcount;                                         // the slots in use, per query (at item_begin; <= n_items of them) and how many
@@ -132,6 +133,44 @@ __global__ __launch_bounds__(GB_THREADS) void gb_iota_kernel(GbArgs a) {
     if (a.gq[qi].iota) ((uint32_t*)a.ids)[i] = (uint32_t)(i - a.gq[qi].item_begin);
 }
 
+// ---- a pure vector search's FLAT queries (tsgpu_vector_search_grouped_batch): distance segment -> items ----
+// The flat branch puts every filter id through the Topster except the query document (:3686), the ids without a stored vector and the ids beyond the
+// threshold (:3699-3704). vec_flat_ragged_distances_kernel wrote the first two as NaN; this kernel keeps the others, IN LIST ORDER (ascending ids: what
+// gb_hit_vd and the select kernel's record lookup search), as the query's items (id, vec_dist_score) and counts them. One workgroup per flat query walks
+// its segment in GB_THREADS-id tiles (a flat list is shorter than flat_search_cutoff and a batch has many queries); the running offset is workgroup-uniform
+// (block_compact hands every thread the tile's total). 8 bytes read + 8 written per kept id.
+struct GbVecFlat {
+    uint64_t dist_off;        // first distance of the query's segment in the ragged array
+    uint64_t list_off;        // first id of its list in the uploaded lists
+    uint64_t item_begin;      // where its items go (room for n_list of them)
+    uint32_t n_list;
+    float threshold;
+    uint32_t abs;             // cosine: std::abs of the distance (:3699)
+    uint32_t query;           // its index in the batch (the count's slot)
+};
+__global__ __launch_bounds__(GB_THREADS) void gb_vec_items_kernel(const GbVecFlat* __restrict__ fl, const float* __restrict__ dist, const uint32_t* __restrict__ list_ids,
+                                                                  uint32_t* __restrict__ ids, float* __restrict__ vd, uint32_t* __restrict__ counts) {
+    static_assert(GB_THREADS == KW_THREADS, "block_compact sums KW_THREADS / 64 wave totals");
+    __shared__ uint32_t s_wave_cnt[GB_THREADS / 64];
+    const GbVecFlat f = fl[blockIdx.x];
+    uint32_t kept = 0;                                                       // (workgroup-uniform)
+    for (uint32_t base = 0; base < f.n_list; base += GB_THREADS) {           // (workgroup-uniform trip count: every thread reaches the barriers)
+        const uint32_t j = base + threadIdx.x;
+        float d = 0.0f;
+        bool keep = false;
+        if (j < f.n_list) {
+            d = dist[f.dist_off + j];
+            if (f.abs) d = fabsf(d);
+            keep = !(d != d) && !(d > f.threshold);
+        }
+        uint32_t total;
+        const uint32_t my = block_compact(keep, s_wave_cnt, total);
+        if (keep) { ids[f.item_begin + kept + my] = list_ids[f.list_off + j]; vd[f.item_begin + kept + my] = d; }
+        kept += total;
+    }
+    if (threadIdx.x == 0) counts[f.query] = kept;
+}
+
 // ---- scoring of every matched id ----
 template <int TMAX, bool VQ = false>                                         // 3: every query of the batch has <= 3 lists (a fifth of the registers of the 10-token form)
 __global__ __launch_bounds__(TMAX <= 3 ? GB_THREADS : 64) void gb_score_kernel(IndexView ix, GbArgs a) {      // (the 10-token form holds 40 positions per thread: one wave per workgroup)
@@ -147,6 +186,8 @@ __global__ __launch_bounds__(TMAX <= 3 ? GB_THREADS : 64) void gb_score_kernel(I
     ScoredHit h;
     h.s0 = h.s1 = h.s2 = h.text_match = 0; h.off_words = 0;
     if (!live) {
+    } else if (g.vec) {
+        h = sort_scores(ix, q, seq_id, 0, 0, false, a.vd[i]);                 // the vector branch: text-match slot 0, the id's vec_dist_score (src/index.cpp:3709-3711)
     } else if (g.wildcard) {
         h = sort_scores(ix, q, seq_id, 100, 0, false, 0.0f);                 // Index::search_wildcard: the text-match slot is the constant 100 (src/index.cpp:6728-6730)
     } else {
@@ -178,6 +219,16 @@ __global__ __launch_bounds__(TMAX <= 3 ? GB_THREADS : 64) void gb_score_kernel(I
     // the group column holds get_distinct_id's result per seq_id; a document beyond it has no value in any group_by field (src/index.cpp:7104-7111)
     a.dkey[i] = (col < ix.n_columns && seq_id < ix.column_len[col]) ? (unsigned long long)ix.columns[col][seq_id]
                                                                  : (g.group_missing_values ? 1ull : (unsigned long long)seq_id);
+}
+
+// KV::vector_distance of a delivered hit: a vector query's item ids ascend (one combination), so the hit's item is the lower bound of its key; every other
+// query delivers -1
+__device__ inline float gb_hit_vd(const GbArgs& a, const GbQuery& g, uint32_t key) {
+    if (!g.vec) return -1.0f;
+    const uint32_t* qids = a.ids + g.item_begin;
+    uint32_t lo = 0, hi = g.n_items;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (qids[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo < g.n_items ? a.vd[g.item_begin + lo] : -1.0f;
 }
 
 __device__ inline uint64_t gb_mix(uint64_t x) {
@@ -436,7 +487,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_select_kernel(GbArgs a) {
             a.out.keys[o] = a.ids[b];
             a.out.scores[o * 3 + 0] = e0; a.out.scores[o * 3 + 1] = e1; a.out.scores[o * 3 + 2] = e2;
             a.out.text_match[o] = msi == 0 ? e0 : (msi == 1 ? e1 : (msi == 2 ? e2 : 0));
-            a.out.vector_distance[o] = -1.0f;
+            a.out.vector_distance[o] = gb_hit_vd(a, g, a.ids[b]);
             a.out.match_score_index[o] = (int8_t)msi;
             a.out_qidx[o] = a.qidx_of_combo[g.first_combo + a.pass[b]];
         }
@@ -446,8 +497,9 @@ __global__ __launch_bounds__(GB_THREADS) void gb_select_kernel(GbArgs a) {
         // the record of the entry: its id's position in a combination's ascending ids — the one its group's table names as the best record
         uint32_t lo = 0;
         for (uint32_t c = g.first_combo; c < g.first_combo + g.n_combos; c++) {
-            const uint32_t b = (uint32_t)(a.combo_begin[c] - g.item_begin);
-            uint32_t hi = (uint32_t)(a.combo_begin[c + 1] - g.item_begin);
+            // (one combination: all of the query's items — a vector query's items are followed by the slots of the ids its compaction dropped, not by the next combination)
+            const uint32_t b = g.n_combos == 1 ? 0u : (uint32_t)(a.combo_begin[c] - g.item_begin);
+            uint32_t hi = g.n_combos == 1 ? g.n_items : (uint32_t)(a.combo_begin[c + 1] - g.item_begin);
             const uint32_t end = hi;
             lo = b;
             while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (qids[mid] < key) lo = mid + 1; else hi = mid; }
@@ -467,7 +519,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_select_kernel(GbArgs a) {
             a.out.keys[o] = key;
             a.out.scores[o * 3 + 0] = tk.s0[r]; a.out.scores[o * 3 + 1] = tk.s1[r]; a.out.scores[o * 3 + 2] = tk.s2[r];
             a.out.text_match[o] = msi == 0 ? tk.s0[r] : (msi == 1 ? tk.s1[r] : (msi == 2 ? tk.s2[r] : 0));
-            a.out.vector_distance[o] = -1.0f;
+            a.out.vector_distance[o] = gb_hit_vd(a, g, key);
             a.out.match_score_index[o] = (int8_t)msi;
             a.out_qidx[o] = a.qidx_of_combo[g.first_combo + a.pass[g.item_begin + lo]];
         }
@@ -613,7 +665,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_members_kernel(GbArgs a) {
             a.out.keys[o] = (uint64_t)bk;
             a.out.scores[o * 3 + 0] = b0; a.out.scores[o * 3 + 1] = b1; a.out.scores[o * 3 + 2] = b2;
             a.out.text_match[o] = msi == 0 ? b0 : (msi == 1 ? b1 : (msi == 2 ? b2 : 0));
-            a.out.vector_distance[o] = -1.0f;
+            a.out.vector_distance[o] = gb_hit_vd(a, g, (uint32_t)bk);
             a.out.match_score_index[o] = (int8_t)msi;
             a.out_qidx[o] = a.qidx_of_combo[g.first_combo + a.pass[g.item_begin + bx]];
         }
@@ -706,7 +758,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_chunk_kernel(GbArgs a) {
         a.out.keys[o] = (uint64_t)tk.key[j];
         a.out.scores[o * 3 + 0] = tk.s0[j]; a.out.scores[o * 3 + 1] = tk.s1[j]; a.out.scores[o * 3 + 2] = tk.s2[j];
         a.out.text_match[o] = msi == 0 ? tk.s0[j] : (msi == 1 ? tk.s1[j] : (msi == 2 ? tk.s2[j] : 0));
-        a.out.vector_distance[o] = -1.0f;
+        a.out.vector_distance[o] = gb_hit_vd(a, g, (uint32_t)tk.key[j]);
         a.out.match_score_index[o] = (int8_t)msi;
         a.out_qidx[o] = a.qidx_of_combo[g.first_combo + a.pass[g.item_begin + gb_record_of_key(a, g, (uint32_t)tk.key[j])]];
     }

@@ -589,6 +589,11 @@ int tsgpu_get_counter(tsgpu_ctx* ctx, const char* name, uint64_t* out) {
     if (!strcmp(name, "vec_search_pq_flat_queries")) { *out = ctx->vec_search_pq_flat_queries.load(); return ok(); }     // tsgpu_vector_search_batch_per_query, cumulative
     if (!strcmp(name, "vec_search_pq_kcut_queries")) { *out = ctx->vec_search_pq_kcut_queries.load(); return ok(); }
     if (!strcmp(name, "vec_search_pq_flat_lists")) { *out = ctx->vec_search_pq_flat_lists.load(); return ok(); }         // distinct flat lists uploaded
+    if (!strcmp(name, "vec_grouped_flat_queries")) { *out = ctx->vec_grouped_flat_queries.load(); return ok(); }       // tsgpu_vector_search_grouped_batch
+    if (!strcmp(name, "vec_grouped_kcut_queries")) { *out = ctx->vec_grouped_kcut_queries.load(); return ok(); }
+    if (!strcmp(name, "vec_grouped_items")) { *out = ctx->vec_grouped_items.load(); return ok(); }
+    if (!strcmp(name, "vec_grouped_syncs")) { *out = ctx->vec_grouped_syncs.load(); return ok(); }
+    if (!strcmp(name, "vec_grouped_sync_us")) { *out = ctx->vec_grouped_sync_us.load(); return ok(); }
     if (!strcmp(name, "vec_search_pq_flat_launches")) { *out = ctx->vec_search_pq_flat_launches.load(); return ok(); }   // launches of vec_flat_ragged_distances_kernel
     if (!strcmp(name, "vec_filter_h2d_bytes")) { *out = ctx->vec_filter_h2d_bytes; return ok(); }
     if (!strcmp(name, "vec_filter_stage_us")) { *out = ctx->vec_filter_stage_us; return ok(); }

@@ -18,6 +18,7 @@ struct GroupByScratch {
     // match_score_index | text_match | vector_distance] (the optional arrays last: only the requested prefix crosses PCIe).
     DevBuf in, ff, zero, out, work, loglog;          // work = per-item records + member lists + per-group offsets (never initialised, never delivered)
     DevBuf ids_dev;                                  // the id pass' matched ids when they never leave the device (a batch of single-field keyword queries)
+    DevBuf vec_in;                                   // a vector batch's flat queries: [count per query | GbVecFlat per flat query] (gb_vec_items_kernel)
     PinBuf h_in, h_out;
     // staging of a coalesced round (gb_coalesced, under ctx->mu): grow-only — value-initialising 4 MB of vectors per round cost a millisecond
     std::vector<uint64_t> c_keys, c_nm, c_dk, c_gtot, c_gcnt;
@@ -28,7 +29,7 @@ struct GroupByScratch {
     std::vector<int32_t> c_st, c_co;
     std::vector<uint8_t> c_regs;
     void release() {
-        DevBuf* b[] = {&in, &ff, &zero, &out, &work, &loglog, &ids_dev};
+        DevBuf* b[] = {&in, &ff, &zero, &out, &work, &loglog, &ids_dev, &vec_in};
         for (auto* x : b) x->release();
         h_in.release(); h_out.release();
     }
@@ -37,6 +38,17 @@ struct GbLayout {                                    // byte offsets inside a bl
     size_t at = 0;
     size_t take(size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; }
 };
+struct GbInLayout { size_t gq, qd, mf, cb, qx, fk, ids, vd, end; };      // the input block (GroupByScratch::in)
+static GbInLayout gb_in_layout(uint32_t n_queries, uint32_t n_combos, size_t n_forced, size_t id_bytes, size_t vd_bytes) {
+    GbLayout L;
+    GbInLayout o;
+    const uint32_t ncz = std::max<uint32_t>(n_combos, 1);
+    o.gq = L.take(sizeof(GbQuery) * n_queries); o.qd = L.take(sizeof(KwQueryDev) * ncz); o.mf = L.take(sizeof(KwQueryMF) * ncz);
+    o.cb = L.take(((size_t)n_combos + 1) * 8); o.qx = L.take((size_t)ncz * 4); o.fk = L.take(n_forced * 8 + 8);
+    o.ids = L.take(id_bytes); o.vd = L.take(vd_bytes);
+    o.end = L.at;
+    return o;
+}
 
 // LogLogBeta::cardinality() (include/loglogbeta.h:30-44 betaApprox, :62-75 regSumAndZeros, :107-121) from the sketch's registers, or from how many
 // registers hold each value (gb_select_kernel's histogram): the reference adds 2^-register over the registers IN ORDER; with no register above 38 every
@@ -73,15 +85,16 @@ static bool gb_loglog_cardinality_hist(const uint32_t* hist, uint64_t* out) {   
 
 // tsgpu_kw_query -> the device description the scoring functions read, in the multi-field form (a single query_by field is the one-field case of
 // compute_aggregated_score); the predicates and fills are kw_translate.h's, the order of the checks is this entry point's (sort slots first)
-static int gb_translate(const tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query& in, bool wildcard, KwQueryDev& q, KwQueryMF& m) {
+static int gb_translate(const tsgpu_ctx* ctx, const Snapshot& snap, const tsgpu_kw_query& in, bool wildcard, KwQueryDev& q, KwQueryMF& m, bool vec = false) {
     memset(&q, 0, sizeof q);
     memset(&m, 0xFF, sizeof m);
     q.mf_index = KW_NONE;
     q.syn_orig_num_tokens = -1;
     if (in.n_sort > TSGPU_MAX_SORT_KEYS) return TSGPU_ERR_INVALID;
-    if (const int sort_rc = check_sort_slots(const_cast<tsgpu_ctx*>(ctx), in.sort, in.n_sort, false, false, nullptr)) return sort_rc;
+    // (a vector query, tsgpu_vector_search_grouped_batch: _vector_distance is a sort key, the kinds >= TSGPU_SORT_EVAL are not served; it has sort slots only)
+    if (const int sort_rc = check_sort_slots(const_cast<tsgpu_ctx*>(ctx), in.sort, in.n_sort, vec, vec, nullptr)) return sort_rc;
     kw_fill_sort_slots(in, q);
-    if (wildcard) { m.n_fields = 0; return TSGPU_OK; }
+    if (wildcard || vec) { m.n_fields = 0; return TSGPU_OK; }
     if (!kw_token_count_ok(in) || !kw_field_count_ok(in) || !kw_dropped_count_ok(in)) return TSGPU_ERR_UNSUPPORTED;
     if (in.match_type > TSGPU_SUM_SCORE) return TSGPU_ERR_INVALID;
     m.driver_token = 0;
@@ -110,8 +123,13 @@ void tsgpu_groupby_destroy(tsgpu_ctx* ctx) {
 //     the count of earlier matching passes (which is a property of all shards together);
 //   present_elsewhere: per COMBINATION, the tokens that exist on ANOTHER shard (a token missing here is then an empty list, not a dropped token: kw_dispatch).
 // A q = * query of a context with a doc range matches the seq_ids the context OWNS.
+// `vec` (nullable; tsgpu_vector_search_grouped_batch, one combination per query that carries the sort slots only): the THIRD source of items beside the id pass and the
+//   host-built wildcard lists — query i's items are (seq_id, vec_dist_score) pairs: a k-cut query's come from the host (vec->q[i].ids / .vd, ascending ids), a flat
+//   query's are compacted on the device out of its segment of the ragged distance array (gb_vec_items_kernel), whose per-query counts the host needs before it can
+//   size the group tables: one small download and one stream sync per batch with flat queries ("vec_grouped_syncs"). No id pass runs.
 static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const uint32_t* cfirst, const tsgpu_group_by* groups, uint32_t n_queries,
-                           tsgpu_hits* out, tsgpu_grouped_hits* gout, uint32_t* query_index, tsgpu_id_lists** ids_out, const tsgpu::GbShard* shard = nullptr) {
+                           tsgpu_hits* out, tsgpu_grouped_hits* gout, uint32_t* query_index, tsgpu_id_lists** ids_out, const tsgpu::GbShard* shard = nullptr,
+                           const tsgpu::GbVec* vec = nullptr) {
     (void)hipSetDevice(ctx->device);
     const std::shared_ptr<const Snapshot> snap_ref = ctx->snapshot();
     const Snapshot& snap = *snap_ref;
@@ -137,11 +155,11 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             memset(&gq[i], 0, sizeof(GbQuery));
             const uint32_t c0 = cfirst[i], nc = cfirst[i + 1] - c0;
             gq[i].first_combo = c0; gq[i].n_combos = nc;
-            int st = TSGPU_OK;
-            if (nc == 0 || nc > (uint32_t)KW_MAX_CANDIDATE_PASSES || (gb.wildcard && nc != 1)) st = TSGPU_ERR_INVALID;
+            int st = vec ? vec->q[i].status : TSGPU_OK;                     // (what the vector front refused stays refused, with its code)
+            if (st == TSGPU_OK && (nc == 0 || nc > (uint32_t)KW_MAX_CANDIDATE_PASSES || (gb.wildcard && nc != 1))) st = TSGPU_ERR_INVALID;
             for (uint32_t c = c0; st == TSGPU_OK && c < c0 + nc; c++) {
                 const tsgpu_kw_query& in = combos[c];
-                st = gb_translate(ctx, snap, in, gb.wildcard != 0, qd[c], mf[c]);
+                st = gb_translate(ctx, snap, in, gb.wildcard != 0, qd[c], mf[c], vec != nullptr);
                 if (st == TSGPU_OK && (in.n_filter != 0 && !in.filter_ids)) st = TSGPU_ERR_INVALID;
                 if (st == TSGPU_OK && (in.n_excluded != 0 && !in.excluded_ids)) st = TSGPU_ERR_INVALID;
             }
@@ -150,9 +168,14 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             uint32_t k = 1;
             const bool forced = shard && shard->forced_begin;
             if (st == TSGPU_OK) {
-                k = resolve_topster_size(ctx, combos[c0]);                 // ONE collector for all combinations (src/index.cpp:3506-3514)
+                k = vec ? vec->q[i].capacity : resolve_topster_size(ctx, combos[c0]);     // ONE collector for all combinations (src/index.cpp:3506-3514); the vector branch sized its own
                 if (forced) k = std::max<uint32_t>(1, shard->forced_begin[i + 1] - shard->forced_begin[i]);     // (the given groups: all of them are returned)
                 if (k > TSGPU_MAX_TOPK) st = TSGPU_ERR_UNSUPPORTED;
+                else if (vec) {
+                    // a vector query cannot produce more groups than it has items: the strides must hold B = min(capacity, item bound) groups / their hits
+                    const uint32_t B_ = std::min(k, vec->q[i].bound);
+                    if (B_ > gout->g_stride || (uint64_t)B_ * (gb.first_pass ? 1u : gb.group_limit) > out->k_stride) st = TSGPU_ERR_INVALID;
+                }
                 else if (k > gout->g_stride) st = TSGPU_ERR_INVALID;
                 else if ((uint64_t)k * (gb.first_pass ? 1u : gb.group_limit) > out->k_stride) st = TSGPU_ERR_INVALID;   // second pass: slot r * group_limit + j
             }
@@ -160,7 +183,7 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             if (st != TSGPU_OK) continue;
             max_k = std::max(max_k, k);
             gq[i].k = k; gq[i].group_limit = gb.group_limit; gq[i].column = gb.column;
-            gq[i].first_pass = gb.first_pass ? 1 : 0; gq[i].group_missing_values = gb.group_missing_values ? 1 : 0; gq[i].wildcard = gb.wildcard ? 1 : 0;
+            gq[i].first_pass = gb.first_pass ? 1 : 0; gq[i].group_missing_values = gb.group_missing_values ? 1 : 0; gq[i].wildcard = gb.wildcard ? 1 : 0; gq[i].vec = vec ? 1 : 0;
             if (forced) { gq[i].forced = 1; gq[i].forced_begin = shard->forced_begin[i]; gq[i].n_forced = shard->forced_begin[i + 1] - shard->forced_begin[i]; }
             gq[i].dedupe = (!gb.first_pass && nc > 1) ? 1 : 0;             // a second pass counts a document once, with its greatest KV (group_doc_seq_ids + replace-unless-smaller)
             any_dedupe = any_dedupe || gq[i].dedupe;
@@ -180,7 +203,7 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             std::vector<tsgpu_kw_query> kq;
             std::vector<uint32_t> kq_of;
             for (uint32_t i = 0; i < n_queries; i++) {
-                if (status[i] != TSGPU_OK) continue;
+                if (status[i] != TSGPU_OK || vec) continue;              // (a vector query's items are its front's: no id pass)
                 const tsgpu_kw_query& in = combos[cfirst[i]];
                 if (groups[i].wildcard) {
                     // Index::search_wildcard ranks the filter ids (every seq_id without a filter) minus the excluded ids (src/index.cpp:6674-6676)
@@ -244,6 +267,47 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
                 }
             }
         }
+        // ---- step 1, vector form: the item space is [the k-cut queries' items, from the host | one segment of n_filter slots per flat query, in the order of the
+        //      ragged distance array]; gb_vec_items_kernel fills the head of every flat segment and counts it (the slots behind a query's count are never read) ----
+        std::vector<uint64_t> v_begin(vec ? n_queries : 0, 0);
+        std::vector<uint32_t> v_count(vec ? n_queries : 0, 0);
+        uint64_t v_host_items = 0, v_space = 0;
+        if (vec) {
+            if (!ctx->groupby) ctx->groupby = new GroupByScratch;
+            GroupByScratch& S = *ctx->groupby;
+            for (uint32_t i = 0; i < n_queries; i++)
+                if (status[i] == TSGPU_OK && !vec->q[i].flat) { v_begin[i] = v_host_items; v_count[i] = vec->q[i].n; v_host_items += vec->q[i].n; }
+            v_space = v_host_items;
+            std::vector<GbVecFlat> fl;
+            for (uint32_t i = 0; i < n_queries; i++) {
+                const tsgpu::GbVecQuery& vq = vec->q[i];
+                if (status[i] != TSGPU_OK || !vq.flat) continue;
+                v_begin[i] = v_space;
+                fl.push_back(GbVecFlat{vq.dist_off, vq.list_off, v_space, vq.n_list, vq.threshold, vec->abs ? 1u : 0u, i});
+                v_space += vq.n_list;
+            }
+            if (v_space > 0x7FFFFFFFull) return fail(TSGPU_ERR_UNSUPPORTED, "tsgpu_vector_search_grouped_batch: more than 2^31 candidate ids in one batch; split it");
+            if (!fl.empty()) {
+                const GbInLayout I0 = gb_in_layout(n_queries, n_combos, 0, std::max<uint64_t>(v_space, 1) * 4, std::max<uint64_t>(v_space, 1) * 4);
+                const size_t cnt_bytes = ((size_t)n_queries * 4 + 15) & ~(size_t)15;
+                int rc0;
+                if ((rc0 = S.in.reserve(I0.end)) || (rc0 = S.vec_in.reserve(cnt_bytes + fl.size() * sizeof(GbVecFlat)))) return rc0;
+                TSGPU_HIP_TRY(hipMemcpyAsync((char*)S.vec_in.p + cnt_bytes, fl.data(), fl.size() * sizeof(GbVecFlat), hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL(gb_vec_items_kernel, dim3((uint32_t)fl.size()), dim3(GB_THREADS), 0, s, (const GbVecFlat*)((char*)S.vec_in.p + cnt_bytes), vec->dist_dev,
+                                   vec->list_ids_dev, (uint32_t*)((char*)S.in.p + I0.ids), (float*)((char*)S.in.p + I0.vd), S.vec_in.as<uint32_t>());
+                TSGPU_HIP_TRY(hipGetLastError());
+                std::vector<uint32_t> cnt(n_queries, 0);                  // (only the flat queries' slots are written)
+                TSGPU_HIP_TRY(hipMemcpyAsync(cnt.data(), S.vec_in.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost, s));
+                const uint64_t t_sync = now_us();
+                TSGPU_HIP_TRY(hipStreamSynchronize(s));                   // the counts size the group tables
+                ctx->vec_grouped_syncs.fetch_add(1);
+                ctx->vec_grouped_sync_us.fetch_add(now_us() - t_sync);    // (the wait covers the distance launches and the compaction queued before it)
+                for (const GbVecFlat& f : fl) v_count[f.query] = cnt[f.query];
+            }
+            uint64_t items = 0;
+            for (uint32_t i = 0; i < n_queries; i++) { num_matched[i] = v_count[i]; items += v_count[i]; }
+            ctx->vec_grouped_items.fetch_add(items);
+        }
         const uint64_t t_ids = now_us();
         // ---- layout ----
         uint64_t n_items = 0, n_slots = 0, n_blocks = 0, n_sblocks = 0;
@@ -251,16 +315,16 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
         std::vector<uint32_t> qidx_of_combo(std::max<uint32_t>(n_combos, 1), 0);
         for (uint32_t i = 0; i < n_queries; i++) {
             GbQuery& g = gq[i];
-            g.item_begin = n_items; g.tab_off = n_slots;
+            g.item_begin = vec ? v_begin[i] : n_items; g.tab_off = n_slots;
             g.run = status[i] == TSGPU_OK ? 1 : 0;
             g.iota = iota[i];
             uint64_t n = 0, gap = 0;
             uint32_t matched_before = 0;                  // searched_queries.size() at the time of a pass: the earlier combinations that matched anything (:5580-5585)
             for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; c++) {
-                combo_begin[c] = n_items + n + gap;
+                combo_begin[c] = vec ? v_begin[i] : n_items + n + gap;
                 qidx_of_combo[c] = (shard && shard->pass_mask) ? c - cfirst[i] : matched_before;      // (shard form: the hit's PASS travels; "matched anything" is decided over all shards)
                 uint64_t nc = 0;
-                if (g.run) nc = iota[i] ? ctx->num_docs : (groups[i].wildcard ? wild_ids[i].size() : tsgpu_id_lists_count(idl.get(), kw_index[c]));
+                if (g.run) nc = vec ? v_count[i] : iota[i] ? ctx->num_docs : (groups[i].wildcard ? wild_ids[i].size() : tsgpu_id_lists_count(idl.get(), kw_index[c]));
                 // a user query that FAILED after the id pass (one of its combinations ran out of time, ...) while another of its combinations succeeded: with the
                 // ids on the device, kw_dispatch packed the successful combination's ids into ids_dev like everybody else's. They are a GAP of the item space
                 // (nobody reads them: the query has no items), or every later query's combo_begin / item_begin would be short by that many ids
@@ -277,9 +341,10 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             n_blocks += (n + GB_THREADS - 1) / GB_THREADS;
             g.first_sblock = (uint32_t)n_sblocks;
             n_sblocks += (n + GB_SCATTER_ITEMS - 1) / GB_SCATTER_ITEMS;
-            n_items += n + gap;
+            if (!vec) n_items += n + gap;
             n_slots += size + 1;                          // + the slot of the key ~0
         }
+        if (vec) n_items = v_space;                       // (the item arrays span the flat segments whole: item_begin is a slot of that space)
         combo_begin[n_combos] = n_items;
         // second passes: the chunk work lists of the big groups and their partial top-L buffers
         uint64_t n_pw = 0, n_pb = 0;
@@ -298,11 +363,10 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
         const uint32_t gs = gout->g_stride, ks = out->k_stride;
         const size_t n_out = (size_t)n_queries * ks, n_g = (size_t)n_queries * gs;
         const uint64_t ni = std::max<uint64_t>(n_items, 1);
-        GbLayout Lin, Lff, Lzero, Lout, Lwork;
-        const uint32_t ncz = std::max<uint32_t>(n_combos, 1);
-        const size_t i_gq = Lin.take(sizeof(GbQuery) * n_queries), i_qd = Lin.take(sizeof(KwQueryDev) * ncz), i_mf = Lin.take(sizeof(KwQueryMF) * ncz),
-                     i_cb = Lin.take(((size_t)n_combos + 1) * 8), i_qx = Lin.take((size_t)ncz * 4),
-                     i_fk = Lin.take(((shard && shard->forced_begin) ? (size_t)shard->forced_begin[n_queries] : 0) * 8 + 8), i_ids = Lin.take(ids_on_dev ? 16 : ni * 4);
+        GbLayout Lff, Lzero, Lout, Lwork;
+        // (a vector batch: the same offsets as the layout gb_vec_items_kernel wrote the flat items through — the block's size depends on the item SPACE, not on the counts)
+        const GbInLayout Lin = gb_in_layout(n_queries, n_combos, (shard && shard->forced_begin) ? (size_t)shard->forced_begin[n_queries] : 0, ids_on_dev ? 16 : ni * 4, vec ? ni * 4 : 16);
+        const size_t i_gq = Lin.gq, i_qd = Lin.qd, i_mf = Lin.mf, i_cb = Lin.cb, i_qx = Lin.qx, i_fk = Lin.fk, i_ids = Lin.ids, i_vd = Lin.vd;
         const size_t f_hkey = Lff.take(n_slots * 8), f_hbest = Lff.take(n_slots * 4), f_hrank = Lff.take(n_slots * 4),
                      f_dkey = Lff.take(any_dedupe ? n_slots * 4 : 16), f_dbest = Lff.take(any_dedupe ? n_slots * 4 : 16);      // the document tables of the second passes over several combinations
         const size_t z_hcount = Lzero.take(n_slots * 4), z_gcount = Lzero.take((size_t)n_queries * 4), z_ticket = Lzero.take(n_g * 4);
@@ -322,15 +386,16 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
                      w_pb2 = Lwork.take(std::max<uint64_t>(n_pb, 1) * 8), w_pbk = Lwork.take(std::max<uint64_t>(n_pb, 1) * 8);
         const size_t out_bytes = query_index ? Lout.at : (out->vector_distance ? end_vd : (out->text_match ? end_tm : end_required));      // what the caller asked for, as a prefix
         int rc;
-        if ((rc = S.in.reserve(Lin.at)) || (rc = S.ff.reserve(Lff.at)) || (rc = S.zero.reserve(Lzero.at)) || (rc = S.out.reserve(Lout.at)) || (rc = S.work.reserve(Lwork.at)) ||
+        if ((rc = S.in.reserve(Lin.end)) || (rc = S.ff.reserve(Lff.at)) || (rc = S.zero.reserve(Lzero.at)) || (rc = S.out.reserve(Lout.at)) || (rc = S.work.reserve(Lwork.at)) ||
             (rc = S.h_out.reserve(out_bytes <= (4u << 20) ? out_bytes : o_gdkey)))
             return rc;
         // the pinned staging holds the descriptions and the id arrays that come FROM the host: not the ids the id pass left on the device, not the ids
         // gb_iota_kernel writes for q = * (40 MB of pinned memory per 10M documents otherwise)
         uint64_t host_items_end = 0;
-        for (uint32_t i = 0; !ids_on_dev && i < n_queries; i++)
+        for (uint32_t i = 0; !ids_on_dev && !vec && i < n_queries; i++)
             if (gq[i].run && gq[i].n_items && !iota[i]) host_items_end = std::max<uint64_t>(host_items_end, (uint64_t)gq[i].item_begin + gq[i].n_items);
-        if ((rc = S.h_in.reserve(i_ids + 16 + host_items_end * 4))) return rc;
+        // (a vector batch: the k-cut queries' ids and distances, the head of the item space; the flat queries' items are on the device already)
+        if ((rc = S.h_in.reserve(vec ? i_ids + 32 + v_host_items * 8 : i_ids + 16 + host_items_end * 4))) return rc;
         const bool want_loglog = any_first;
         if (want_loglog && (rc = S.loglog.reserve((size_t)n_queries * GB_LOGLOG_M))) return rc;
         {
@@ -341,7 +406,13 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             memcpy(hin + i_cb, combo_begin.data(), ((size_t)n_combos + 1) * 8);
             memcpy(hin + i_qx, qidx_of_combo.data(), (size_t)n_combos * 4);
             if (shard && shard->forced_begin && shard->forced_begin[n_queries]) memcpy(hin + i_fk, shard->forced_keys, (size_t)shard->forced_begin[n_queries] * 8);
-            for (uint32_t i = 0; !ids_on_dev && i < n_queries; i++) {
+            float* hvd = (float*)(hin + ((i_ids + (size_t)v_host_items * 4 + 15) & ~(size_t)15));      // staged behind the ids; uploaded to i_vd
+            for (uint32_t i = 0; vec && i < n_queries; i++) {
+                if (!gq[i].run || gq[i].n_items == 0 || vec->q[i].flat) continue;
+                memcpy(hin + i_ids + (size_t)gq[i].item_begin * 4, vec->q[i].ids, (size_t)gq[i].n_items * 4);
+                memcpy(hvd + gq[i].item_begin, vec->q[i].vd, (size_t)gq[i].n_items * 4);
+            }
+            for (uint32_t i = 0; !ids_on_dev && !vec && i < n_queries; i++) {
                 if (!gq[i].run || gq[i].n_items == 0 || iota[i]) continue;
                 if (groups[i].wildcard) { memcpy(hin + i_ids + (size_t)gq[i].item_begin * 4, wild_ids[i].data(), (size_t)gq[i].n_items * 4); continue; }
                 for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; c++) {       // the combinations' ascending id lists, one after the other
@@ -350,7 +421,12 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
                 }
             }
         }
-        if (ids_on_dev) TSGPU_HIP_TRY(hipMemcpyAsync(S.in.p, S.h_in.p, i_ids, hipMemcpyHostToDevice, s));      // the descriptions only: the ids are where the id pass gathered them
+        if (vec) {
+            // the descriptions with the k-cut ids behind them in one copy, the k-cut distances in a second one (their array starts behind the whole id space)
+            TSGPU_HIP_TRY(hipMemcpyAsync(S.in.p, S.h_in.p, i_ids + (size_t)v_host_items * 4, hipMemcpyHostToDevice, s));
+            if (v_host_items) TSGPU_HIP_TRY(hipMemcpyAsync((char*)S.in.p + i_vd, (char*)S.h_in.p + ((i_ids + (size_t)v_host_items * 4 + 15) & ~(size_t)15), (size_t)v_host_items * 4, hipMemcpyHostToDevice, s));
+        }
+        else if (ids_on_dev) TSGPU_HIP_TRY(hipMemcpyAsync(S.in.p, S.h_in.p, i_ids, hipMemcpyHostToDevice, s));      // the descriptions only: the ids are where the id pass gathered them
         else if (!any_iota) TSGPU_HIP_TRY(hipMemcpyAsync(S.in.p, S.h_in.p, i_ids + (size_t)n_items * 4, hipMemcpyHostToDevice, s));      // (pinned: the ids' one extra host copy buys a DMA at link speed)
         else {
             // the descriptions, then the id arrays of the queries that have one; the others' ids (0 .. num_docs - 1) are written by gb_iota_kernel
@@ -372,7 +448,7 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
         a.n_pw = (uint32_t)n_pw; a.pw_list = (uint32_t*)(dw + w_pwlist); a.pw_count = (uint32_t*)(dw + w_pwcount); a.pw_n = (uint32_t*)(dw + w_pwn);
         a.g_pfirst = (uint32_t*)(dw + w_pfirst); a.g_nchunk = (uint32_t*)(dw + w_nchunk); a.g_ticket = (uint32_t*)(dz + z_ticket);
         a.pb_s0 = (int64_t*)(dw + w_pb0); a.pb_s1 = (int64_t*)(dw + w_pb1); a.pb_s2 = (int64_t*)(dw + w_pb2); a.pb_key = (int64_t*)(dw + w_pbk);
-        a.n_items = n_items; a.ids = ids_on_dev ? S.ids_dev.as<uint32_t>() : (const uint32_t*)(din + i_ids);
+        a.n_items = n_items; a.ids = ids_on_dev ? S.ids_dev.as<uint32_t>() : (const uint32_t*)(din + i_ids); a.vd = vec ? (const float*)(din + i_vd) : nullptr;
         a.s0 = (int64_t*)(dw + w_s0); a.s1 = (int64_t*)(dw + w_s1); a.s2 = (int64_t*)(dw + w_s2); a.dkey = (unsigned long long*)(dw + w_dkey); a.rslot = (uint32_t*)(dw + w_rslot);
         a.hkey = (unsigned long long*)(dff + f_hkey); a.hbest = (uint32_t*)(dff + f_hbest); a.hrank = (uint32_t*)(dff + f_hrank);
         a.hcount = (uint32_t*)(dz + z_hcount); a.gcount = (uint32_t*)(dz + z_gcount);
@@ -387,7 +463,7 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
         IndexView v = make_view(ctx, snap);
         for (int e = 0; e < 4; e++) if (!ctx->aux_ev[e]) TSGPU_HIP_TRY(hipEventCreate(&ctx->aux_ev[e]));      // (tsgpu_last_aux_timings: four marks per batch, ~2 us each)
         TSGPU_HIP_TRY(hipEventRecord(ctx->aux_ev[0], s));
-        if (n_items) {
+        if (n_blocks) {                                   // (item slots without items — a failed query's gap, the ids a vector query's compaction dropped — launch nothing)
             if (any_iota) hipLaunchKernelGGL(gb_iota_kernel, dim3((uint32_t)n_blocks), dim3(GB_THREADS), 0, s, a);
             uint32_t max_lists = 0;
             for (uint32_t i = 0; i < n_queries; i++) if (gq[i].run) for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; c++) max_lists = std::max(max_lists, qd[c].n_lists);
@@ -404,7 +480,7 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
         else if (max_k + GB_THREADS <= 1024) hipLaunchKernelGGL((gb_select_kernel<1024>), dim3(n_queries), dim3(GB_THREADS), 0, s, a);
         else hipLaunchKernelGGL((gb_select_kernel<2048>), dim3(n_queries), dim3(GB_THREADS), 0, s, a);
         TSGPU_HIP_TRY(hipEventRecord(ctx->aux_ev[2], s));
-        if (any_second && n_items) {
+        if (any_second && n_sblocks) {
             hipLaunchKernelGGL(gb_scatter_kernel, dim3((uint32_t)n_sblocks), dim3(GB_THREADS), 0, s, a);
             const uint64_t pairs = (uint64_t)n_queries * gs;
             hipLaunchKernelGGL(gb_members_kernel, dim3((uint32_t)((pairs + GB_THREADS / 64 - 1) / (GB_THREADS / 64))), dim3(GB_THREADS), 0, s, a);
@@ -489,7 +565,12 @@ static int gb_batch_locked(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const u
             // all_result_ids per user query: the union of its combinations' matched ids, ascending (id_buff -> sort + unique + or_scalar, src/index.cpp:5565-5578)
             std::unique_ptr<tsgpu_id_lists> il(new tsgpu_id_lists);
             std::vector<uint32_t> flat(n_items);
-            if (ids_on_dev && n_items) TSGPU_HIP_TRY(hipMemcpy(flat.data(), S.ids_dev.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
+            if (vec) {
+                // nearest_ids (src/index.cpp:3724-3732): the items' ids, ascending — the k-cut queries' from the staging, the flat segments from where the compaction left them
+                if (v_host_items) memcpy(flat.data(), (const char*)S.h_in.p + i_ids, (size_t)v_host_items * 4);
+                if (n_items > v_host_items) TSGPU_HIP_TRY(hipMemcpy(flat.data() + v_host_items, din + i_ids + (size_t)v_host_items * 4, (size_t)(n_items - v_host_items) * 4, hipMemcpyDeviceToHost));
+            }
+            else if (ids_on_dev && n_items) TSGPU_HIP_TRY(hipMemcpy(flat.data(), S.ids_dev.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
             else if (n_items) {
                 for (uint32_t i = 0; i < n_queries; i++) {
                     if (!gq[i].n_items) continue;
@@ -638,6 +719,26 @@ int gb_shard_batch(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const uint32_t*
     if (n_queries == 0) return ok();
     std::lock_guard<std::mutex> lk(ctx->mu);
     return gb_batch_locked(ctx, combos, cfirst, groups, n_queries, out, gout, query_index, nullptr, shard);
+}
+// the grouped core for tsgpu_vector_search_grouped_batch (tsgpu_vec.hip: classification, the k-NN batch, the ragged distances); the caller holds ctx->mu.
+// Query i is one "combination" that carries params[i]'s sort slots; groups[i].wildcard is ignored.
+int gb_vector_batch(tsgpu_ctx* ctx, const tsgpu_vec_query* params, const tsgpu_group_by* groups, uint32_t n_q, tsgpu_hits* out, tsgpu_grouped_hits* gout,
+                    tsgpu_id_lists** ids_out, const GbVec* vec) {
+    try {
+        std::vector<tsgpu_kw_query> qs(n_q);
+        memset(qs.data(), 0, qs.size() * sizeof(tsgpu_kw_query));
+        std::vector<tsgpu_group_by> gs(groups, groups + n_q);
+        std::vector<uint32_t> cf((size_t)n_q + 1);
+        for (uint32_t i = 0; i < n_q; i++) {
+            cf[i] = i;
+            gs[i].wildcard = 0;
+            if (vec->q[i].status != TSGPU_OK) continue;                  // (n_sort was checked by the front)
+            qs[i].n_sort = params[i].n_sort;
+            for (uint32_t j = 0; j < params[i].n_sort; j++) qs[i].sort[j] = params[i].sort[j];
+        }
+        cf[n_q] = n_q;
+        return gb_batch_locked(ctx, qs.data(), cf.data(), gs.data(), n_q, out, gout, nullptr, ids_out, nullptr, vec);
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, "tsgpu_vector_search_grouped_batch: host allocation failed"); }
 }
 }  // namespace tsgpu
 

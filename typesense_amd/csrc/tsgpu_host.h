@@ -625,6 +625,9 @@ struct tsgpu_ctx {
     uint64_t vec_filter_direct_queries = 0, vec_filter_scan_queries = 0;   // counters: filtered queries answered by either route
     // tsgpu_vector_search_batch_per_query (cumulative; calls run concurrently): queries answered by either branch, distinct flat lists uploaded, ragged launches
     std::atomic<uint64_t> vec_search_pq_flat_queries{0}, vec_search_pq_kcut_queries{0}, vec_search_pq_flat_lists{0}, vec_search_pq_flat_launches{0};
+    // tsgpu_vector_search_grouped_batch (cumulative): queries grouped per branch, items that reached the grouped core, stream syncs spent on the flat queries' item counts
+    // (vec_grouped_sync_us: host time spent waiting in those syncs — the wait includes the distance launches and the compaction queued before the download)
+    std::atomic<uint64_t> vec_grouped_flat_queries{0}, vec_grouped_kcut_queries{0}, vec_grouped_items{0}, vec_grouped_syncs{0}, vec_grouped_sync_us{0};
     uint64_t vec_flat_group_max_bytes = 1ull << 30;  // ... bytes of the ragged distance array ONE launch of it fills (option; tests lower it to force the split)
     uint64_t vec_filter_h2d_bytes = 0;               // counter: bytes of id lists (+ their offsets) uploaded for per-query filters
     uint64_t vec_filter_stage_us = 0, vec_filter_build_us = 0;   // counters: host time staging + uploading the lists / time of the bitmap or survivor-list build kernels that follow (only under vec_count_rescored: it costs a sync per group)
@@ -805,6 +808,18 @@ struct GbShard { const uint64_t* forced_keys; const uint32_t* forced_begin; cons
 uint64_t gb_registers_cardinality(const uint8_t* regs);      // LogLogBeta::cardinality() of 16384 registers (the shards' sketches merge by the registers' maxima)
 int gb_shard_batch(tsgpu_ctx* ctx, const tsgpu_kw_query* combos, const uint32_t* cfirst, const tsgpu_group_by* groups, uint32_t n_queries, tsgpu_hits* out, tsgpu_grouped_hits* gout,
                    uint32_t* query_index, const GbShard* shard);
+// group_by for the pure vector search (tsgpu_vector_search_grouped_batch): what tsgpu_vec.hip's front hands the grouped core (tsgpu_groupby.inc.h) per query.
+// status != TSGPU_OK: the front refused the query. capacity = the Topster's; bound = the most items the query can have (k of a k-cut query, n_filter of a flat one).
+// A FLAT query's items are made on the device from its segment of the ragged distance array (dist_off) and its list among the uploaded lists (list_off, n_list ids);
+// a K-CUT query's come from the host: n (id, vec_dist_score) pairs, ids ascending.
+struct GbVecQuery {
+    int32_t status; uint32_t flat, capacity, bound;
+    uint64_t dist_off, list_off; uint32_t n_list; float threshold;
+    const uint32_t* ids; const float* vd; uint32_t n;
+};
+struct GbVec { const GbVecQuery* q; const float* dist_dev; const uint32_t* list_ids_dev; bool abs; };
+int gb_vector_batch(tsgpu_ctx* ctx, const tsgpu_vec_query* params, const tsgpu_group_by* groups, uint32_t n_q, tsgpu_hits* out, tsgpu_grouped_hits* gout,
+                    tsgpu_id_lists** ids_out, const GbVec* vec);      // caller holds ctx->mu
 int group_kw_kth(tsgpu_ctx* ctx, const tsgpu_hits* local_dev, uint32_t n_q, uint32_t k, uint32_t n_shards, const uint32_t* caps_dev, int64_t* kth, hipStream_t s);
 int group_kw_prune_pack(tsgpu_ctx* ctx, const tsgpu_hits* local_dev, uint32_t n_q, uint32_t n_pad, uint32_t k, uint32_t words, const uint32_t* caps_dev, const int64_t* kth_all,
                         uint32_t n_shards, uint32_t per, uint32_t n_dst, uint64_t slice_words, uint64_t* block, uint32_t* cursor, hipStream_t s);

@@ -1940,88 +1940,116 @@ static uint32_t flat_topster_size(const tsgpu_vec_query& p) {     // :3506-3512
 // One ragged distance array, filled by one launch of vec_flat_ragged_distances_kernel per group of consecutive slots whose segments fit
 // "vec_flat_group_max_bytes" (1 GiB: what one launch's tile table and output window cover; the array itself is whole, the ONE ranking call reads all of
 // it), then kw_vector_flat_search ranks every slot's segment with its own threshold, list and Topster size. Lock and buffers as vector_search_flat.
-static int vector_search_pq_flat(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const std::vector<uint32_t>& fq, const float* Qh, uint32_t dim,
-                                 PqHits& res, std::vector<uint32_t>& slot_q, tsgpu_id_lists** lists_out) {
-    const uint32_t n = (uint32_t)fq.size();
-    std::map<std::pair<const uint32_t*, uint32_t>, uint32_t> list_of;
+// The distance stage, shared with tsgpu_vector_search_grouped_batch: pq_flat_plan lays the slots out on the host, pq_flat_distances_locked (ctx->mu held by
+// the caller) translates and uploads the lists and enqueues the launches on ctx->stream WITHOUT synchronising; the stage owns the host arrays the uploads read
+// and the device buffers (per call: another flat search may run while this one ranks), which are parked, not freed, when it goes.
+struct PqFlatStage {
+    uint32_t n = 0, n_lists = 0;
+    bool cosine = false;
+    uint64_t total = 0;                                // distances in the ragged array
     std::vector<const tsgpu_vec_query*> list_owner;
+    std::vector<uint32_t> slot_q, slot_list;           // per slot: its caller index, its list
+    std::vector<uint64_t> list_off, off;               // first row / id of every list (+ the end); first distance of every slot
+    std::vector<float> thr, Qf;
+    std::vector<VecFlatQuery> qa;
+    std::vector<VecFlatTile> tiles;
+    std::vector<size_t> group_tile0;                   // first tile of every group (+ the end)
+    std::vector<uint32_t> rows, ids;
+    DevBuf d_dist, d_rows, d_q, d_qa, d_tiles, d_ids;  // d_ids: the lists' ids themselves, laid out like the rows (the grouped call's compaction reads them)
+    ~PqFlatStage() { for (DevBuf* x : {&d_dist, &d_rows, &d_q, &d_qa, &d_tiles, &d_ids}) if (x->p) { deferred_frees().park(x->p, x->cap, false); x->p = nullptr; x->cap = 0; } }
+};
+static void pq_flat_plan(const tsgpu_ctx* ctx, const tsgpu_vec_query* params, const std::vector<uint32_t>& fq, const float* Qh, uint32_t dim, PqFlatStage& st) {
+    const uint32_t n = st.n = (uint32_t)fq.size();
+    std::map<std::pair<const uint32_t*, uint32_t>, uint32_t> list_of;
     std::vector<uint32_t> lq(n), ord(n);
     for (uint32_t j = 0; j < n; j++) {
         const tsgpu_vec_query& p = params[fq[j]];
-        const auto it = list_of.emplace(std::make_pair(p.filter_ids, p.n_filter), (uint32_t)list_owner.size());
-        if (it.second) list_owner.push_back(&p);
+        const auto it = list_of.emplace(std::make_pair(p.filter_ids, p.n_filter), (uint32_t)st.list_owner.size());
+        if (it.second) st.list_owner.push_back(&p);
         lq[j] = it.first->second;
         ord[j] = j;
     }
     std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return lq[a] < lq[b]; });
-    const uint32_t n_lists = (uint32_t)list_owner.size();
-    std::vector<uint64_t> list_off(n_lists + 1, 0);
-    for (uint32_t l = 0; l < n_lists; l++) list_off[l + 1] = list_off[l] + list_owner[l]->n_filter;
+    const uint32_t n_lists = st.n_lists = (uint32_t)st.list_owner.size();
+    st.list_off.assign(n_lists + 1, 0);
+    for (uint32_t l = 0; l < n_lists; l++) st.list_off[l + 1] = st.list_off[l] + st.list_owner[l]->n_filter;
     // per slot: its query, its segment, the position of its query document; the tiles, group by group
-    slot_q.resize(n);
-    std::vector<VecFlatQuery> qa(n);
-    std::vector<uint64_t> off(n);
-    std::vector<float> thr(n), Qf((size_t)n * dim);
-    std::vector<VecFlatTile> tiles;
-    std::vector<size_t> group_tile0(1, 0);             // first tile of every group (+ the end)
+    st.slot_q.resize(n); st.slot_list.resize(n); st.qa.resize(n); st.off.resize(n); st.thr.resize(n); st.Qf.resize((size_t)n * dim);
+    st.group_tile0.assign(1, 0);
     uint64_t total = 0, group_bytes = 0;
     for (uint32_t s = 0; s < n; s++) {
         const uint32_t qi = fq[ord[s]];
         const tsgpu_vec_query& p = params[qi];
-        slot_q[s] = qi;
-        memcpy(Qf.data() + (size_t)s * dim, Qh + (size_t)qi * dim, (size_t)dim * 4);
+        st.slot_q[s] = qi; st.slot_list[s] = lq[ord[s]];
+        memcpy(st.Qf.data() + (size_t)s * dim, Qh + (size_t)qi * dim, (size_t)dim * 4);
         uint32_t skip = VEC_FLAT_NO_SKIP;
         if (p.query_doc_given) {                         // the query document itself is left out (:3686): its position in the list, if it is a member
             const uint32_t* at = std::lower_bound(p.filter_ids, p.filter_ids + p.n_filter, p.query_seq_id);
             if (at != p.filter_ids + p.n_filter && *at == p.query_seq_id) skip = (uint32_t)(at - p.filter_ids);
         }
-        qa[s] = VecFlatQuery{list_off[lq[ord[s]]], total, skip, 0};
-        off[s] = total; thr[s] = p.distance_threshold;
+        st.qa[s] = VecFlatQuery{st.list_off[lq[ord[s]]], total, skip, 0};
+        st.off[s] = total; st.thr[s] = p.distance_threshold;
         const uint64_t bytes = 4ull * p.n_filter;
-        if (group_bytes && group_bytes + bytes > ctx->vec_flat_group_max_bytes) { group_tile0.push_back(tiles.size()); group_bytes = 0; }
+        if (group_bytes && group_bytes + bytes > ctx->vec_flat_group_max_bytes) { st.group_tile0.push_back(st.tiles.size()); group_bytes = 0; }
         group_bytes += bytes;
-        for (uint32_t first = 0; first < p.n_filter; first += VEC_FLAT_TILE) tiles.push_back(VecFlatTile{s, first, std::min<uint32_t>(VEC_FLAT_TILE, p.n_filter - first)});
+        for (uint32_t first = 0; first < p.n_filter; first += VEC_FLAT_TILE) st.tiles.push_back(VecFlatTile{s, first, std::min<uint32_t>(VEC_FLAT_TILE, p.n_filter - first)});
         total += p.n_filter;
     }
-    group_tile0.push_back(tiles.size());
-    DevBuf d_dist, d_rows, d_q, d_qa, d_tiles;         // per call (another flat search may run while this one ranks): parked, not freed, on exit
-    struct Park { DevBuf* b[5]; ~Park() { for (DevBuf* x : b) if (x->p) { deferred_frees().park(x->p, x->cap, false); x->p = nullptr; x->cap = 0; } } } park{{&d_dist, &d_rows, &d_q, &d_qa, &d_tiles}};
-    bool cosine = false;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        VecField* f = get_field(ctx, vec_field_id);
-        if (!f || f->dim != dim) return fail(TSGPU_ERR_NOT_FOUND, "tsgpu_vector_search_batch_per_query: unknown vector field");
-        cosine = f->metric == TSGPU_METRIC_COSINE;
-        hipStream_t s = ctx->stream;
-        std::vector<uint32_t> rows(list_off[n_lists]);
-        for (uint32_t l = 0; l < n_lists; l++) {         // getDataByLabel throws for an unknown / deleted label: "likely not found", the id is skipped (:3355-3360)
-            const uint32_t* ids = list_owner[l]->filter_ids;
-            uint32_t* dst = rows.data() + list_off[l];
-            for (uint32_t i = 0; i < list_owner[l]->n_filter; i++) { uint32_t r; dst[i] = (f->find_row(ids[i], r) && f->h_ok[r]) ? r : 0xFFFFFFFFu; }
+    st.group_tile0.push_back(st.tiles.size());
+    st.total = total;
+}
+static int pq_flat_distances_locked(tsgpu_ctx* ctx, uint32_t vec_field_id, uint32_t dim, PqFlatStage& st, bool upload_ids, const char* who) {
+    (void)hipSetDevice(ctx->device);
+    VecField* f = get_field(ctx, vec_field_id);
+    if (!f || f->dim != dim) return fail(TSGPU_ERR_NOT_FOUND, std::string(who) + ": unknown vector field");
+    st.cosine = f->metric == TSGPU_METRIC_COSINE;
+    hipStream_t s = ctx->stream;
+    const uint32_t n = st.n, n_lists = st.n_lists;
+    st.rows.resize(st.list_off[n_lists]);
+    if (upload_ids) st.ids.resize(st.list_off[n_lists]);
+    for (uint32_t l = 0; l < n_lists; l++) {         // getDataByLabel throws for an unknown / deleted label: "likely not found", the id is skipped (:3355-3360)
+        const uint32_t* ids = st.list_owner[l]->filter_ids;
+        uint32_t* dst = st.rows.data() + st.list_off[l];
+        for (uint32_t i = 0; i < st.list_owner[l]->n_filter; i++) { uint32_t r; dst[i] = (f->find_row(ids[i], r) && f->h_ok[r]) ? r : 0xFFFFFFFFu; }
+        if (upload_ids) memcpy(st.ids.data() + st.list_off[l], ids, (size_t)st.list_owner[l]->n_filter * 4);
+    }
+    int rc;
+    if ((rc = st.d_dist.reserve(std::max<size_t>(st.total * 4, 16))) || (rc = st.d_rows.reserve(st.rows.size() * 4)) || (rc = st.d_q.reserve(st.Qf.size() * 4)) ||
+        (rc = st.d_qa.reserve(st.qa.size() * sizeof(VecFlatQuery))) || (rc = st.d_tiles.reserve(st.tiles.size() * sizeof(VecFlatTile)))) return rc;
+    if (upload_ids) {
+        if ((rc = st.d_ids.reserve(std::max<size_t>(st.ids.size() * 4, 16)))) return rc;
+        TSGPU_HIP_TRY(hipMemcpyAsync(st.d_ids.p, st.ids.data(), st.ids.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (f->n_rows == 0) TSGPU_HIP_TRY(hipMemsetAsync(st.d_dist.p, 0xFF, st.total * 4, s));      // (no row to read: every id is "not found", NaN)
+    else {
+        TSGPU_HIP_TRY(hipMemcpyAsync(st.d_rows.p, st.rows.data(), st.rows.size() * 4, hipMemcpyHostToDevice, s));
+        TSGPU_HIP_TRY(hipMemcpyAsync(st.d_q.p, st.Qf.data(), st.Qf.size() * 4, hipMemcpyHostToDevice, s));
+        TSGPU_HIP_TRY(hipMemcpyAsync(st.d_qa.p, st.qa.data(), st.qa.size() * sizeof(VecFlatQuery), hipMemcpyHostToDevice, s));
+        TSGPU_HIP_TRY(hipMemcpyAsync(st.d_tiles.p, st.tiles.data(), st.tiles.size() * sizeof(VecFlatTile), hipMemcpyHostToDevice, s));
+        if (st.cosine) hipLaunchKernelGGL(vec_normalize_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, s, st.d_q.as<float>(), n, dim);     // (:3362-3364)
+        for (size_t g = 0; g + 1 < st.group_tile0.size(); g++) {
+            const size_t t0 = st.group_tile0[g], nt = st.group_tile0[g + 1] - t0;
+            hipLaunchKernelGGL(vec_flat_ragged_distances_kernel, dim3((uint32_t)nt), dim3(VEC_THREADS), 0, s, (const float*)f->X.as<float>(), (const float*)st.d_q.as<float>(), dim,
+                               (const uint32_t*)st.d_rows.as<uint32_t>(), (const VecFlatQuery*)st.d_qa.as<VecFlatQuery>(), (const VecFlatTile*)st.d_tiles.as<VecFlatTile>() + t0,
+                               st.d_dist.as<float>(), ctx->vec_ip_lanes);
+            ctx->vec_search_pq_flat_launches.fetch_add(1);
         }
-        int rc;
-        if ((rc = d_dist.reserve(std::max<size_t>(total * 4, 16))) || (rc = d_rows.reserve(rows.size() * 4)) || (rc = d_q.reserve(Qf.size() * 4)) ||
-            (rc = d_qa.reserve(qa.size() * sizeof(VecFlatQuery))) || (rc = d_tiles.reserve(tiles.size() * sizeof(VecFlatTile)))) return rc;
-        if (f->n_rows == 0) TSGPU_HIP_TRY(hipMemsetAsync(d_dist.p, 0xFF, total * 4, s));      // (no row to read: every id is "not found", NaN)
-        else {
-            TSGPU_HIP_TRY(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
-            TSGPU_HIP_TRY(hipMemcpyAsync(d_q.p, Qf.data(), Qf.size() * 4, hipMemcpyHostToDevice, s));
-            TSGPU_HIP_TRY(hipMemcpyAsync(d_qa.p, qa.data(), qa.size() * sizeof(VecFlatQuery), hipMemcpyHostToDevice, s));
-            TSGPU_HIP_TRY(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(VecFlatTile), hipMemcpyHostToDevice, s));
-            if (cosine) hipLaunchKernelGGL(vec_normalize_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_q.as<float>(), n, dim);     // (:3362-3364)
-            for (size_t g = 0; g + 1 < group_tile0.size(); g++) {
-                const size_t t0 = group_tile0[g], nt = group_tile0[g + 1] - t0;
-                hipLaunchKernelGGL(vec_flat_ragged_distances_kernel, dim3((uint32_t)nt), dim3(VEC_THREADS), 0, s, (const float*)f->X.as<float>(), (const float*)d_q.as<float>(), dim,
-                                   (const uint32_t*)d_rows.as<uint32_t>(), (const VecFlatQuery*)d_qa.as<VecFlatQuery>(), (const VecFlatTile*)d_tiles.as<VecFlatTile>() + t0,
-                                   d_dist.as<float>(), ctx->vec_ip_lanes);
-                ctx->vec_search_pq_flat_launches.fetch_add(1);
-            }
-            TSGPU_HIP_TRY(hipGetLastError());
-        }
-        TSGPU_HIP_TRY(hipStreamSynchronize(s));         // the ranking runs on a keyword lane's stream (and the host arrays above go out of scope)
+        TSGPU_HIP_TRY(hipGetLastError());
     }
     ctx->vec_search_pq_flat_lists.fetch_add(n_lists);
+    return TSGPU_OK;
+}
+static int vector_search_pq_flat(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const std::vector<uint32_t>& fq, const float* Qh, uint32_t dim,
+                                 PqHits& res, std::vector<uint32_t>& slot_q, tsgpu_id_lists** lists_out) {
+    PqFlatStage st;
+    pq_flat_plan(ctx, params, fq, Qh, dim, st);
+    const uint32_t n = st.n;
+    slot_q = st.slot_q;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (const int rc = pq_flat_distances_locked(ctx, vec_field_id, dim, st, false, "tsgpu_vector_search_batch_per_query")) return rc;
+        TSGPU_HIP_TRY(hipStreamSynchronize(ctx->stream));         // the ranking runs on a keyword lane's stream
+    }
     ctx->vec_search_pq_flat_queries.fetch_add(n);
     std::vector<tsgpu_kw_query> qs(n);
     memset(qs.data(), 0, qs.size() * sizeof(tsgpu_kw_query));
@@ -2033,8 +2061,33 @@ static int vector_search_pq_flat(tsgpu_ctx* ctx, uint32_t vec_field_id, const ts
         q.topster_size = flat_topster_size(p);
         q.filter_ids = p.filter_ids; q.n_filter = p.n_filter;
     }
-    KwVFlat vf{d_dist.as<float>(), 0, 0.0f, cosine, off.data(), thr.data()};
+    KwVFlat vf{st.d_dist.as<float>(), 0, 0.0f, st.cosine, st.off.data(), st.thr.data()};
     return kw_vector_flat_search(ctx, qs.data(), n, &res.h, &vf, lists_out);
+}
+
+// What tsgpu_vector_search_batch refuses as a call for reasons in the parameter block is the query's status in the per-query calls: the block's branch (:3664),
+// its k (:3646, + 1 when the query document passes the functor, :3651-3654) and its Topster capacity (:3506-3512); the callers add their own stride checks.
+struct PqClass { int st; bool flat; uint32_t k, tsz; };
+static PqClass pq_classify(const tsgpu_vec_query& p, uint32_t num_docs, uint64_t n_rows) {
+    PqClass c{TSGPU_OK, false, 0, 0};
+    if (p.n_sort > 3) c.st = TSGPU_ERR_INVALID;
+    else if ((p.n_filter && !p.filter_ids) || (p.n_excluded && !p.excluded_ids)) c.st = TSGPU_ERR_INVALID;
+    else {
+        for (uint32_t j = 0; j < p.n_sort; j++) if (p.sort[j].kind >= TSGPU_SORT_EVAL) c.st = TSGPU_ERR_UNSUPPORTED;
+        c.flat = (p.filter_by_provided || p.n_filter) && p.n_filter != 0 && (uint64_t)p.n_filter < p.flat_search_cutoff;     // :3664
+    }
+    if (c.st != TSGPU_OK) return c;
+    if (c.flat) { c.tsz = flat_topster_size(p); return c; }
+    uint32_t k = p.k == 0 ? p.fetch_size : p.k;                                    // :3646
+    if (k == 0) { c.st = TSGPU_ERR_INVALID; return c; }
+    const bool doc_passes = p.query_doc_given && !(p.n_excluded && std::binary_search(p.excluded_ids, p.excluded_ids + p.n_excluded, p.query_seq_id)) &&
+                            (p.n_filter == 0 || std::binary_search(p.filter_ids, p.filter_ids + p.n_filter, p.query_seq_id));
+    if (doc_passes) k++;                                                           // :3651-3654
+    uint32_t tsz = p.topster_size ? p.topster_size : std::max<uint32_t>(p.fetch_size, TSGPU_DEFAULT_TOPSTER_SIZE);
+    if (!p.topster_size) tsz = std::max<uint32_t>(1, std::min<uint32_t>(tsz, p.n_filter ? p.n_filter : std::max<uint32_t>(num_docs, (uint32_t)n_rows)));   // :3506-3512
+    c.k = k; c.tsz = tsz;
+    if (k > TSGPU_MAX_TOPK) c.st = TSGPU_ERR_UNSUPPORTED;
+    return c;
 }
 
 static int vector_search_pq_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const float* Q, int mem_q, uint32_t n_q, tsgpu_hits* out,
@@ -2064,31 +2117,14 @@ static int vector_search_pq_impl(tsgpu_ctx* ctx, uint32_t vec_field_id, const ts
         // ---- classify: what tsgpu_vector_search_batch refuses as a call for reasons in the parameter block is the query's status here ----
         std::vector<uint32_t> fq, kq, k_of(n_q, 0), tsz_of(n_q, 0);
         for (uint32_t i = 0; i < n_q; i++) {
-            const tsgpu_vec_query& p = params[i];
-            int st = TSGPU_OK;
-            bool flat = false;
-            if (p.n_sort > 3) st = TSGPU_ERR_INVALID;
-            else if ((p.n_filter && !p.filter_ids) || (p.n_excluded && !p.excluded_ids)) st = TSGPU_ERR_INVALID;
-            else {
-                for (uint32_t j = 0; j < p.n_sort; j++) if (p.sort[j].kind >= TSGPU_SORT_EVAL) st = TSGPU_ERR_UNSUPPORTED;
-                flat = (p.filter_by_provided || p.n_filter) && p.n_filter != 0 && (uint64_t)p.n_filter < p.flat_search_cutoff;     // :3664
-            }
+            const PqClass c = pq_classify(params[i], num_docs, n_rows);
+            int st = c.st;
+            const bool flat = c.flat;
             if (st == TSGPU_OK && flat) {
-                const uint32_t tsz = flat_topster_size(p);
-                if (tsz <= TSGPU_MAX_TOPK && out->k_stride < tsz) st = TSGPU_ERR_INVALID;      // (a larger Topster is the ranking's own per-query 501)
+                if (c.tsz <= TSGPU_MAX_TOPK && out->k_stride < c.tsz) st = TSGPU_ERR_INVALID;      // (a larger Topster is the ranking's own per-query 501)
             } else if (st == TSGPU_OK) {
-                uint32_t k = p.k == 0 ? p.fetch_size : p.k;                                    // :3646
-                if (k == 0) st = TSGPU_ERR_INVALID;
-                else {
-                    const bool doc_passes = p.query_doc_given && !(p.n_excluded && std::binary_search(p.excluded_ids, p.excluded_ids + p.n_excluded, p.query_seq_id)) &&
-                                            (p.n_filter == 0 || std::binary_search(p.filter_ids, p.filter_ids + p.n_filter, p.query_seq_id));
-                    if (doc_passes) k++;                                                       // :3651-3654
-                    uint32_t tsz = p.topster_size ? p.topster_size : std::max<uint32_t>(p.fetch_size, TSGPU_DEFAULT_TOPSTER_SIZE);
-                    if (!p.topster_size) tsz = std::max<uint32_t>(1, std::min<uint32_t>(tsz, p.n_filter ? p.n_filter : std::max<uint32_t>(num_docs, (uint32_t)n_rows)));   // :3506-3512
-                    if (k > TSGPU_MAX_TOPK) st = TSGPU_ERR_UNSUPPORTED;
-                    else if (out->k_stride < std::min<uint32_t>(tsz, k)) st = TSGPU_ERR_INVALID;
-                    k_of[i] = k; tsz_of[i] = tsz;
-                }
+                if (out->k_stride < std::min<uint32_t>(c.tsz, c.k)) st = TSGPU_ERR_INVALID;
+                k_of[i] = c.k; tsz_of[i] = c.tsz;
             }
             if (st != TSGPU_OK) {
                 out->status[i] = st; out->n_hits[i] = 0;
@@ -2151,6 +2187,103 @@ int tsgpu_vector_search_batch_per_query_ids(tsgpu_ctx* ctx, uint32_t vec_field_i
                                             tsgpu_id_lists** ids_out) {
     if (!ids_out) return fail(TSGPU_ERR_INVALID, "tsgpu_vector_search_batch_per_query_ids: ids_out is NULL");
     return vector_search_pq_impl(ctx, vec_field_id, params, Q, mem_q, n_q, out, ids_out);
+}
+
+// ---- group_by for the pure vector search (include/tsgpu.h: tsgpu_vector_search_grouped_batch). The reference groups inside the loop of the ungrouped branch
+// (src/index.cpp:3677-3723): get_distinct_id per surviving id, topster->add(&kv) into the distinct Topster, groups_processed[distinct_id]++. Here the front is the
+// per-query call's (pq_classify, ONE filtered k-NN batch, the ragged flat distances) and the distinct Topster is the grouped core's (tsgpu_groupby.inc.h):
+//   k-cut queries: the k-NN results come to the host; every query keeps its prefix, loses its query document (:3686), takes abs() for cosine and the threshold
+//     (:3699-3704), and hands its (id, vec_dist_score) pairs to the core in id order (at most 1 025 of them);
+//   flat queries: the distances stay on the device; gb_vec_items_kernel turns every segment into items (kw_groupby.hip.h).
+// ctx->mu is held from the flat distances to the delivery, as the grouped keyword call holds it (the k-NN batch before takes and releases it by itself).
+int tsgpu_vector_search_grouped_batch(tsgpu_ctx* ctx, uint32_t vec_field_id, const tsgpu_vec_query* params, const tsgpu_group_by* groups, const float* Q, int mem_q, uint32_t n_q,
+                                      tsgpu_hits* out, tsgpu_grouped_hits* gout, tsgpu_id_lists** ids_out) {
+    static const char* who = "tsgpu_vector_search_grouped_batch";
+    if (ids_out) *ids_out = nullptr;
+    if (!ctx || !out || !gout || (n_q != 0 && (!params || !groups || !Q))) return fail(TSGPU_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (n_q == 0) { if (ids_out) { *ids_out = new (std::nothrow) tsgpu_id_lists; if (*ids_out) (*ids_out)->begin.assign(1, 0); } return ok(); }
+    if (out->mem != TSGPU_MEM_HOST) return fail(TSGPU_ERR_UNSUPPORTED, std::string(who) + ": host outputs only");
+    if (!out->keys || !out->scores || !out->n_hits || !out->status) return fail(TSGPU_ERR_INVALID, std::string(who) + ": keys / scores / n_hits / status are required");
+    if (!gout->n_groups || !gout->distinct_key || !gout->group_size || !gout->group_found || gout->g_stride == 0 || out->k_stride == 0)
+        return fail(TSGPU_ERR_INVALID, std::string(who) + ": n_groups / distinct_key / group_size / group_found and the strides are required");
+    if (ctx->doc_range_set) return fail(TSGPU_ERR_UNSUPPORTED, std::string(who) + ": not served by a doc-range shard");
+    try {
+        uint32_t num_docs, dim; uint64_t n_rows; int metric;
+        std::vector<float> Qcopy;
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            VecField* f = get_field(ctx, vec_field_id);
+            if (!f) return fail(TSGPU_ERR_NOT_FOUND, std::string(who) + ": unknown vector field");
+            num_docs = ctx->num_docs; dim = f->dim; n_rows = f->n_rows; metric = f->metric;
+            if (mem_q == TSGPU_MEM_DEVICE) {
+                (void)hipSetDevice(ctx->device);
+                Qcopy.resize((size_t)n_q * dim);
+                TSGPU_HIP_TRY(hipMemcpyAsync(Qcopy.data(), Q, Qcopy.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+                TSGPU_HIP_TRY(hipStreamSynchronize(ctx->stream));
+            }
+        }
+        const float* Qh = mem_q == TSGPU_MEM_DEVICE ? Qcopy.data() : Q;
+        std::vector<tsgpu::GbVecQuery> vq(n_q);
+        std::vector<uint32_t> fq, kq;
+        for (uint32_t i = 0; i < n_q; i++) {
+            const PqClass c = pq_classify(params[i], num_docs, n_rows);
+            tsgpu::GbVecQuery& v = vq[i];
+            memset(&v, 0, sizeof v);
+            v.status = c.st; v.flat = c.flat ? 1u : 0u; v.capacity = c.tsz;
+            v.bound = c.flat ? params[i].n_filter : c.k;
+            if (c.st == TSGPU_OK) (c.flat ? fq : kq).push_back(i);
+        }
+        // ---- k-cut queries: ONE filtered exact k-NN at the largest k; every query keeps its prefix ----
+        std::vector<std::vector<uint32_t>> kc_ids(kq.size());
+        std::vector<std::vector<float>> kc_vd(kq.size());
+        if (!kq.empty()) {
+            const uint32_t nk = (uint32_t)kq.size();
+            uint32_t K = 0;
+            std::vector<float> Qk((size_t)nk * dim);
+            std::vector<tsgpu_vec_filter> fl(nk);
+            for (uint32_t j = 0; j < nk; j++) {
+                const tsgpu_vec_query& p = params[kq[j]];
+                K = std::max(K, vq[kq[j]].bound);
+                memcpy(Qk.data() + (size_t)j * dim, Qh + (size_t)kq[j] * dim, (size_t)dim * 4);
+                fl[j] = tsgpu_vec_filter{p.n_filter ? 1u : 0u, p.n_filter, p.n_filter ? p.filter_ids : nullptr, p.n_excluded, p.n_excluded ? p.excluded_ids : nullptr};
+            }
+            KnnHost kh;
+            kh.dist.assign((size_t)nk * K, 0.f); kh.lab.assign((size_t)nk * K, 0); kh.cnt.assign(nk, 0);
+            if (const int rc = tsgpu_vec_knn_batch_filtered(ctx, vec_field_id, Qk.data(), TSGPU_MEM_HOST, nk, K, fl.data(), kh.dist.data(), kh.lab.data(), kh.cnt.data(), TSGPU_MEM_HOST)) return rc;
+            std::vector<std::pair<uint64_t, float>> hits;
+            for (uint32_t j = 0; j < nk; j++) {
+                const tsgpu_vec_query& p = params[kq[j]];
+                const uint32_t n = std::min(kh.cnt[j], vq[kq[j]].bound);
+                hits.clear();
+                for (uint32_t i = 0; i < n; i++) hits.emplace_back(kh.lab[(size_t)j * K + i], kh.dist[(size_t)j * K + i]);
+                std::sort(hits.begin(), hits.end(), [](const auto& a, const auto& b) { return a.first < b.first; });   // :3389
+                for (const auto& h : hits) {
+                    if (p.query_doc_given && h.first == p.query_seq_id) continue;                         // :3686
+                    const float d = metric == TSGPU_METRIC_COSINE ? std::fabs(h.second) : h.second;        // :3699
+                    if (d > p.distance_threshold) continue;                                                 // :3702
+                    kc_ids[j].push_back((uint32_t)h.first); kc_vd[j].push_back(d);
+                }
+                vq[kq[j]].ids = kc_ids[j].data(); vq[kq[j]].vd = kc_vd[j].data(); vq[kq[j]].n = (uint32_t)kc_ids[j].size();
+            }
+        }
+        // ---- flat queries: the ragged distances (and the lists' ids) stay on the device ----
+        PqFlatStage st;
+        if (!fq.empty()) pq_flat_plan(ctx, params, fq, Qh, dim, st);
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (!fq.empty()) {
+            if (const int rc = pq_flat_distances_locked(ctx, vec_field_id, dim, st, true, who)) return rc;
+            for (uint32_t s = 0; s < st.n; s++) {
+                tsgpu::GbVecQuery& v = vq[st.slot_q[s]];
+                v.dist_off = st.off[s]; v.list_off = st.list_off[st.slot_list[s]]; v.n_list = params[st.slot_q[s]].n_filter; v.threshold = params[st.slot_q[s]].distance_threshold;
+            }
+        }
+        tsgpu::GbVec gv{vq.data(), st.d_dist.as<float>(), st.d_ids.as<uint32_t>(), metric == TSGPU_METRIC_COSINE};
+        const int rc = tsgpu::gb_vector_batch(ctx, params, groups, n_q, out, gout, ids_out, &gv);
+        if (rc != TSGPU_OK) return rc;
+        ctx->vec_grouped_flat_queries.fetch_add(fq.size());
+        ctx->vec_grouped_kcut_queries.fetch_add(kq.size());
+    } catch (const std::bad_alloc&) { return fail(TSGPU_ERR_NO_MEMORY, std::string(who) + ": host allocation failed"); }
+    return ok();
 }
 
 // reciprocal rank fusion of ONE query, exactly src/index.cpp:4094-4211: `kw` = the keyword Topster content in sort()

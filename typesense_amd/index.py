@@ -858,6 +858,43 @@ class GpuIndex:
             self.L.tsgpu_id_lists_free(lists)
         return hits, ids
 
+    def vector_search_grouped_batch(self, field_id, Q, params, groups, k_stride, g_stride=250, want_ids=False, want_registers=False):
+        """tsgpu_vector_search_grouped_batch: group_by for the pure vector search. params[i] as in vector_search_batch_per_query, groups[i] =
+        (group_limit, column, first_pass, group_missing_values[, ignored]) as in keyword_search_grouped_batch. Returns (Hits, GroupedHits[, id lists])."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, self.vec_dim[field_id])
+        n = Q.shape[0]
+        if len(params) != n or len(groups) != n:
+            raise ValueError("one parameter block and one group_by per query: %d / %d for %d queries" % (len(params), len(groups), n))
+        arr = (B.VecQueryC * max(n, 1))()
+        keep, converted = [], {}                      # every id array stays alive until the call returns; one conversion per array object
+        for i, d in enumerate(params):
+            d = dict(d)
+            for name in ("filter_ids", "excluded_ids"):
+                a = d.get(name)
+                if a is not None:
+                    if id(a) not in converted:
+                        converted[id(a)] = (a, _u32(a))
+                    d[name] = converted[id(a)][1]
+            keep.append(self._fill_vec_query(arr[i], **d))
+        ga = (B.GroupByC * max(n, 1))()
+        for i, g in enumerate(groups):
+            ga[i].group_limit, ga[i].column, ga[i].first_pass, ga[i].group_missing_values = int(g[0]), int(g[1]), int(g[2]), int(g[3])
+        h = Hits(n, k_stride)
+        gh = GroupedHits(n, g_stride, want_registers)
+        hs, gs = h.c_struct(), gh.c_struct()
+        handle = C.c_void_p()
+        self._ck(self.L.tsgpu_vector_search_grouped_batch(self.h, field_id, arr, ga, _vp(Q), B.MEM_HOST, n, C.byref(hs), C.byref(gs), C.byref(handle) if want_ids else None))
+        if not want_ids:
+            return h, gh
+        lists = []
+        try:
+            for q in range(n):
+                cnt = int(self.L.tsgpu_id_lists_count(handle, q))
+                lists.append(np.ctypeslib.as_array(self.L.tsgpu_id_lists_ids(handle, q), shape=(cnt,)).copy() if cnt else np.zeros(0, np.uint32))
+        finally:
+            self.L.tsgpu_id_lists_free(handle)
+        return h, gh, lists
+
     def keyword_aux_scores(self, queries, item_query, item_seq_id):
         """compute_aux_scores' text half: text_match of given documents for the queries' tokens -> int64[n_items]"""
         arr = make_query_array(queries)
