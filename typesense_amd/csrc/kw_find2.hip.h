@@ -50,10 +50,23 @@ static const bool KW_F2_ROUNDS = TSGPU_F2_ROUNDS != 0;
 // per-thread counters: driver ids, block metadata, tile DMA, third.. list probes, hit records; one wave reduction + five atomics per wave at the
 // end into IndexView::touched; slots 7..10: directory-mode work items, pairs, directory-tile pairs, pairs too wide for the tile). A second instantiation launched only under option kw_count_touched — the timed kernel carries none of it.
 // Same results either way (tests/test_emu_keyword.py runs both and compares).
+// The kernel's LDS: of KwSmem<TMAX, 512, false, true, true> the members this kernel touches (the survivor ring, the two tile buffers, the window copies,
+// the compaction counts, the deadline flag) and the LIST TABLE (kw_kernels.hip.h) — one KwProbeRow per token. The top-K threshold, the filter
+// bookkeeping and the counters of the fused kernel are not carried: with them the table would not fit under the 23 040 bytes seven workgroups per CU allow.
+template <int TMAX>
+struct KwFind2Smem {
+    uint32_t q1_id[KW_QCAP], q1_p0[KW_QCAP], q1_p1[KW_QCAP];
+    uint32_t btile[KW_FIND_TILE_WORDS + 2];
+    uint32_t bw_last[2][64], bw_first[2][64], bw_woff[2][64], bw_nb[2][64];
+    uint32_t wave_cnt2[2][KW_THREADS / 64];
+    uint32_t stop;
+    KwProbeRow tab[KW_LIST_TABLE ? TMAX : 1];
+};
+
 template <int TMAX, bool COUNT = false>
 __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQueryDev* __restrict__ queries, const KwWorkItem* __restrict__ work, const KwPartials& part,
                                               uint32_t* __restrict__ hits_all, const uint64_t* __restrict__ hit_off, const uint32_t bid) {
-    __shared__ KwSmem<TMAX, 512, false, true, true> sm;
+    __shared__ KwFind2Smem<TMAX> sm;
     __shared__ uint32_t wave_cnt_b[2][KW_THREADS / 64];        // second half's wave counts (the first half uses sm.wave_cnt2)
     uint32_t* __restrict__ hits = hits_all + hit_off[bid] * (uint64_t)(TMAX + 1);
     __shared__ KwQueryDev sq;
@@ -66,7 +79,16 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         uint32_t* dst = (uint32_t*)&sq;
         for (uint32_t i = t; i < sizeof(KwQueryDev) / 4; i += KW_THREADS) { dst[i] = src[i]; if constexpr (COUNT) cb_meta += 4; }
     }
-    if (t == 0) { sm.q1_cnt = 0; sm.qf_cnt = 0; sm.tk_cnt = 0; sm.have_thr = 0; sm.n_match = 0; sm.n_emit = 0; sm.off_words = 0; }
+    if constexpr (KW_LIST_TABLE) {
+        // the list table: lane k of the second wave fills token k's row from the query in global memory (the copy above is not visible before the barrier)
+        if (t >= 64 && t < 64 + (uint32_t)TMAX) {
+            const KwQueryDev* __restrict__ gq = queries + wi.query;
+            const uint32_t k = t - 64;
+            KwProbeRow r = kw_probe_row_none();
+            if (k < gq->n_lists) { r = kw_probe_row(ix, ix.lists[gq->list[k]]); if constexpr (COUNT) cb_meta += 8u + (uint32_t)sizeof(ListDesc); }
+            sm.tab[k] = r;
+        }
+    }
     __syncthreads();
     const KwQueryDev& q = sq;
     const uint32_t T = q.n_lists;
@@ -247,7 +269,12 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
             for (uint32_t s = 2; s < T && ok; s++) {
                 const uint32_t tok = q.probe_order[s];
                 uint32_t p;
-                if constexpr (COUNT) ok = probe_list<true>(ixp, ixp.lists[q.list[tok]], id, p, &cb_probe);
+                if constexpr (KW_LIST_TABLE) {           // (range test on the table's row, then ONE 8-byte directory load; tok is the same in every lane)
+                    const KwProbeRow row = kw_probe_row_uniform(&sm.tab[tok]);
+                    if constexpr (COUNT) ok = probe_row<true>(ixp, row, q.list[tok], id, p, &cb_probe);
+                    else ok = probe_row(ixp, row, q.list[tok], id, p);
+                }
+                else if constexpr (COUNT) ok = probe_list<true>(ixp, ixp.lists[q.list[tok]], id, p, &cb_probe);
                 else ok = probe_list(ixp, ixp.lists[q.list[tok]], id, p);
 #pragma unroll
                 for (int k = 0; k < TMAX; k++) if ((uint32_t)k == tok) v[k] = p;
@@ -257,7 +284,7 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
         const uint32_t my = block_compact1(ok, sm.wave_cnt2[par], total);
         par ^= 1;
         if (ok) kw_hit_store<TMAX>(hits, qfn + my, id, v);
-        if constexpr (COUNT) { if (ok) cb_rec += 4u * (TMAX + 1); if (lane == 0 && T > 2) cb_meta += (T - 2) * (uint32_t)sizeof(ListDesc); }
+        if constexpr (COUNT) { if (ok) cb_rec += 4u * (TMAX + 1); if (!KW_LIST_TABLE && lane == 0 && T > 2) cb_meta += (T - 2) * (uint32_t)sizeof(ListDesc); }      // (list table: the descriptors were counted once, where the table was filled)
         qfn += total;
         qh = (qh + n_take) & (uint32_t)(KW_QCAP - 1);
         q1n -= n_take;
@@ -452,8 +479,24 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
                 }
             }
         } else if (C.mode == 2) {
-            const IndexView ixp = KW_RELOAD_VIEW(ix);   // (wide / broken runs: the view and the second list's descriptor re-read here)
-            const ListDesc dBp = ixp.lists[q.list[q.probe_order[1]]];
+            const IndexView ixp = KW_RELOAD_VIEW(ix);   // (wide / broken runs: the view re-read here)
+            if constexpr (KW_LIST_TABLE) {
+                // the second list's row from the table; both candidates' directory entries requested before either is looked at
+                const uint32_t tokB = q.probe_order[1];
+                const KwProbeRow row = kw_probe_row_uniform(&sm.tab[tokB]);
+                ProbeReq r0, r1;
+                r0.e = make_uint2(0u, 0u); r0.state = 0; r1.e = make_uint2(0u, 0u); r1.state = 0;
+                if (ok0) probe_row_issue(ixp, row, id0, r0);
+                if (ok1) probe_row_issue(ixp, row, id1, r1);
+                if constexpr (COUNT) {
+                    if (ok0) found0 = probe_row_finish<true>(ixp, q.list[tokB], id0, r0, p10, &cb_probe);
+                    if (ok1) found1 = probe_row_finish<true>(ixp, q.list[tokB], id1, r1, p11, &cb_probe);
+                } else {
+                    if (ok0) found0 = probe_row_finish(ixp, q.list[tokB], id0, r0, p10);
+                    if (ok1) found1 = probe_row_finish(ixp, q.list[tokB], id1, r1, p11);
+                }
+            } else {
+            const ListDesc dBp = ixp.lists[q.list[q.probe_order[1]]];      // (TSGPU_LIST_TABLE=0: the second list's descriptor re-read per pair)
             if constexpr (COUNT) {
                 if (ok0) found0 = probe_list<true>(ixp, dBp, id0, p10, &cb_probe);
                 if (ok1) found1 = probe_list<true>(ixp, dBp, id1, p11, &cb_probe);
@@ -464,6 +507,7 @@ __device__ __forceinline__ void kw_find2_body(const IndexView& ix, const KwQuery
                 if (ok1) probe_issue(ixp, dBp, id1, r1);
                 if (ok0) found0 = probe_finish(ixp, dBp, id0, r0, p10);
                 if (ok1) found1 = probe_finish(ixp, dBp, id1, r1, p11);
+            }
             }
         }
         if (Tl >= 2) { ok0 = ok0 && found0; ok1 = ok1 && found1; }

@@ -426,16 +426,20 @@ __device__ inline void probe_issue(const IndexView& ix, const ListDesc& d, uint3
     if (d.dir_slot && x < ix.iddir_cap_ids) { r.e = ix.iddir[(size_t)(d.dir_slot - 1) * ix.iddir_slot_entries + (x >> 5)]; r.state = 1; }
     else r.state = 2;
 }
-__device__ inline bool probe_search(const IndexView& ix, const ListDesc& d, uint32_t x, uint32_t& pos) {     // (the two-level search of probe_list)
+// (COUNT: *cnt += the bytes of every load of the search, as probe_list counts them)
+template <bool COUNT = false>
+__device__ inline bool probe_search(const IndexView& ix, const ListDesc& d, uint32_t x, uint32_t& pos, uint32_t* cnt = nullptr) {     // (the two-level search of probe_list)
     const uint32_t* __restrict__ bl = ix.blk_last + d.blk_base;
-    const uint32_t lo = guided_lower_bound(d.n_blocks, x, d.first_id, d.last_id, [&](uint32_t i) { return bl[i]; });
+    const uint32_t lo = guided_lower_bound(d.n_blocks, x, d.first_id, d.last_id, [&](uint32_t i) { if constexpr (COUNT) *cnt += 4; return bl[i]; });
     const BlockIds m = ix.blk_ids[d.blk_base + lo];
+    if constexpr (COUNT) *cnt += 16;
     if (x < m.first_id) return false;
     const uint32_t* __restrict__ w = ix.ids_payload + d.ids_base + m.ids_woff;
     const uint32_t target = x - m.first_id;
     const bool w16 = (m.n_ids_bits >> 16) == 16;
     const uint32_t n = m.n_ids_bits & 0xFFFF;
-    const uint32_t l = guided_lower_bound(n, target, 0u, m.last_id - m.first_id, [&](uint32_t i) { return w16 ? (uint32_t)((const uint16_t*)w)[i] : w[i]; });
+    const uint32_t l = guided_lower_bound(n, target, 0u, m.last_id - m.first_id, [&](uint32_t i) { if constexpr (COUNT) *cnt += w16 ? 2 : 4; return w16 ? (uint32_t)((const uint16_t*)w)[i] : w[i]; });
+    if constexpr (COUNT) *cnt += w16 ? 2 : 4;
     if ((w16 ? (uint32_t)((const uint16_t*)w)[l] : w[l]) != target) return false;
     pos = lo * BLOCK_IDS + l;
     return true;
@@ -497,6 +501,73 @@ __device__ inline bool probe_finish(const IndexView& ix, const ListDesc& d, uint
     else return probe_search(ix, d, x, pos);
 }
 
+// LIST TABLE (kw_find2_kernel, kw_score_kernel): what a work item needs of its query's ListDesc records, one compact row per token in LDS, filled
+// once per work item next to the copy of the query (before the kernel's first barrier). A probe / a run load through ix.lists[q.list[tok]] re-reads
+// per-query constants from global memory every time — the handle comes out of LDS, so the compiler keeps it per lane: vector loads of one address by
+// 64 lanes, each a dependent round trip in front of the load that matters (profiles/r12/exp_list_table.txt). TSGPU_LIST_TABLE=0 restores the
+// descriptor loads (tools/ A/B builds only; same results).
+#ifndef TSGPU_LIST_TABLE
+#define TSGPU_LIST_TABLE 1
+#endif
+static const bool KW_LIST_TABLE = TSGPU_LIST_TABLE != 0;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(TSGPU_HIP_EMU)
+#define KW_GLOBAL_AS __attribute__((address_space(1)))       // a pointer into global memory: global_load (vmcnt only), not flat_load (vmcnt AND lgkmcnt)
+#define KW_UNIFORM32(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))      // a value every lane holds alike: into an SGPR
+#else
+#define KW_GLOBAL_AS
+#define KW_UNIFORM32(x) ((uint32_t)(x))
+#endif
+// find kernel: the range test and the directory probe of one list. dir = index of the list's first directory entry in IndexView::iddir, KW_NO_DIR = none
+struct alignas(16) KwProbeRow { uint32_t first_id, last_id, dir_lo, dir_hi; };
+static const unsigned long long KW_NO_DIR = ~0ull;
+__device__ inline KwProbeRow kw_probe_row(const IndexView& ix, const ListDesc& d) {
+    const unsigned long long dir = d.dir_slot ? (unsigned long long)(d.dir_slot - 1) * ix.iddir_slot_entries : KW_NO_DIR;
+    KwProbeRow r; r.first_id = d.first_id; r.last_id = d.last_id; r.dir_lo = (uint32_t)dir; r.dir_hi = (uint32_t)(dir >> 32);
+    return r;
+}
+__device__ inline KwProbeRow kw_probe_row_none() { KwProbeRow r; r.first_id = 0xFFFFFFFFu; r.last_id = 0u; r.dir_lo = r.dir_hi = 0xFFFFFFFFu; return r; }      // (matches no id)
+__device__ inline KwProbeRow kw_probe_row_uniform(const KwProbeRow* row) {          // the row of a token every lane asks about alike
+    KwProbeRow r; r.first_id = KW_UNIFORM32(row->first_id); r.last_id = KW_UNIFORM32(row->last_id); r.dir_lo = KW_UNIFORM32(row->dir_lo); r.dir_hi = KW_UNIFORM32(row->dir_hi);
+    return r;
+}
+// one directory entry: ONE 8-byte global load, requested before either word is looked at
+__device__ __forceinline__ uint2 kw_dir_entry(const uint2* iddir, unsigned long long idx) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(TSGPU_HIP_EMU)
+    const unsigned long long v = ((const KW_GLOBAL_AS unsigned long long*)iddir)[idx];
+    return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+#else
+    return iddir[idx];
+#endif
+}
+// probe_issue / probe_finish / probe_list on a table row. handle = the list's handle: only the two-level search (no directory, a marked entry, an id
+// beyond the directories' range) reads the descriptor itself. Same answers as probe_list.
+__device__ inline void probe_row_issue(const IndexView& ix, const KwProbeRow& r, uint32_t x, ProbeReq& q) {
+    q.e = make_uint2(0u, 0u); q.state = 0;
+    if (x < r.first_id || x > r.last_id) return;
+    const unsigned long long dir = (unsigned long long)r.dir_lo | ((unsigned long long)r.dir_hi << 32);
+    if (dir != KW_NO_DIR && x < ix.iddir_cap_ids) { q.e = kw_dir_entry(ix.iddir, dir + (x >> 5)); q.state = 1; }
+    else q.state = 2;
+}
+template <bool COUNT = false>
+__device__ inline bool probe_row_finish(const IndexView& ix, uint32_t handle, uint32_t x, const ProbeReq& q, uint32_t& pos, uint32_t* cnt = nullptr) {
+    if (q.state == 0) return false;
+    if (q.state == 1) {
+        if constexpr (COUNT) *cnt += 8;
+        const uint32_t b = x & 31u;
+        if (!((q.e.y >> b) & 1u)) return false;
+        if (!(q.e.x & IDDIR_SPLIT)) { pos = q.e.x + (uint32_t)__popc(q.e.y & ((1u << b) - 1u)); return true; }
+    }
+    const ListDesc d = ix.lists[handle];
+    if constexpr (COUNT) *cnt += (uint32_t)sizeof(ListDesc);
+    return probe_search<COUNT>(ix, d, x, pos, cnt);
+}
+template <bool COUNT = false>
+__device__ inline bool probe_row(const IndexView& ix, const KwProbeRow& r, uint32_t handle, uint32_t x, uint32_t& pos, uint32_t* cnt = nullptr) {
+    ProbeReq q;
+    probe_row_issue(ix, r, x, q);
+    return probe_row_finish<COUNT>(ix, handle, x, q, pos, cnt);
+}
+
 // one token's occurrences inside one document (plain string field, src/index.cpp:1323-1348 encoding)
 struct TokRun {
     const uint32_t* w;   // packed offsets of the block
@@ -521,12 +592,75 @@ __device__ inline uint32_t run_raw(const TokRun& r, uint32_t j) {
 // positions.push_back((uint16_t)pos - 1), src/posting_list.cpp:906
 __device__ inline uint32_t run_pos(const TokRun& r, uint32_t j) { return (uint32_t)(uint16_t)((uint16_t)run_raw(r, j) - 1); }
 
-__device__ inline TokRun load_run(const IndexView& ix, const ListDesc& d, uint32_t pos) {
+// score kernel's row of the list table: what a run load needs of a ListDesc (the payload arena's word index, the list's first block)
+struct alignas(16) KwRunRow { uint32_t payload_lo, payload_hi, blk_base, pad; };
+__device__ inline KwRunRow kw_run_row(const ListDesc& d) {
+    KwRunRow r; r.payload_lo = (uint32_t)d.payload_base; r.payload_hi = (uint32_t)(d.payload_base >> 32); r.blk_base = d.blk_base; r.pad = 0;
+    return r;
+}
+struct KwRunSrc { const uint32_t* base; uint32_t blk_base; };          // the same, resolved: the list's payload words, its first block
+__device__ inline KwRunSrc kw_run_src(const IndexView& ix, const ListDesc& d) { KwRunSrc s; s.base = ix.payload + d.payload_base; s.blk_base = d.blk_base; return s; }
+__device__ inline KwRunSrc kw_run_src(const IndexView& ix, const KwRunRow* row) {          // (a row every lane reads alike: scalar registers)
+    KwRunSrc s;
+    s.base = ix.payload + ((unsigned long long)KW_UNIFORM32(row->payload_lo) | ((unsigned long long)KW_UNIFORM32(row->payload_hi) << 32));
+    s.blk_base = KW_UNIFORM32(row->blk_base);
+    return s;
+}
+// a block's 32-byte BlockMeta record as TWO 16-byte loads (the array is 32-byte aligned: tsgpu_index.hip). Field by field the compiler fetched it as a
+// dwordx2 or dwordx4, two ushort and a dword — per token and scored hit.
+__device__ __forceinline__ BlockMeta kw_load_block_meta(const BlockMeta* __restrict__ p) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(TSGPU_HIP_EMU)
+    if constexpr (KW_LIST_TABLE) {
+        // (whole vectors, taken apart in registers: through a union in memory the optimiser turns the copy back into field loads)
+        static_assert(sizeof(BlockMeta) == 32 && offsetof(BlockMeta, n_off) == 16 && offsetof(BlockMeta, n_ids) == 24 && offsetof(BlockMeta, off_bits) == 28, "two 16-byte halves");
+        typedef uint32_t KwU32x4 __attribute__((ext_vector_type(4)));
+        const KwU32x4* __restrict__ h = (const KwU32x4*)p;
+        const KwU32x4 a = h[0], b = h[1];
+        BlockMeta m;
+        m.first_id = a.x; m.ids_woff = a.y; m.oi_woff = a.z; m.off_woff = a.w;
+        m.n_off = b.x; m.off_base = b.y;
+        m.n_ids = (uint16_t)(b.z & 0xFFFFu); m.ids_bits = (uint8_t)((b.z >> 16) & 0xFFu); m.oi_bits = (uint8_t)(b.z >> 24);
+        m.off_bits = (uint8_t)(b.w & 0xFFu); m.pad[0] = m.pad[1] = m.pad[2] = 0;
+        return m;
+    }
+#endif
+    return *p;
+}
+// elements i and i_next (= i + 1, or i in a block's last slot, where the caller takes n_off instead) of a packed offset_index. Up to 16 bits wide both
+// lie inside the 8-byte window at element i's word (shift <= 31, 2 x bits <= 32): ONE load; wider: two windows. The guard word behind every packed
+// array (tsgpu_format.h) covers the window's second word.
+__device__ __forceinline__ unsigned long long kw_window_at(const uint32_t* __restrict__ w, uint32_t idx, uint32_t bits, uint32_t& shift) {
+    const uint64_t bitpos = (uint64_t)idx * bits;
+    const uint32_t* __restrict__ p = w + (bitpos >> 5);
+    shift = (uint32_t)(bitpos & 31);
+    return (uint64_t)p[0] | ((uint64_t)p[1] << 32);
+}
+
+__device__ inline uint32_t unpack_at_nb(const uint32_t* __restrict__ w, uint32_t idx, uint32_t bits) {      // (branch-free; guard word behind every packed array: tsgpu_format.h)
+    uint32_t sh;
+    const uint64_t two = kw_window_at(w, idx, bits, sh);
+    const uint64_t mask = bits >= 32 ? 0xFFFFFFFFull : ((1ull << bits) - 1ull);
+    return (uint32_t)((two >> sh) & mask);
+}
+__device__ inline TokRun load_run(const IndexView& ix, const KwRunSrc& src, uint32_t pos) {
     const uint32_t b = pos >> 8, i = pos & 255;
-    const BlockMeta m = ix.blk_meta[d.blk_base + b];
-    const uint32_t* __restrict__ base = ix.payload + d.payload_base;
-    const uint32_t s = unpack_at(base + m.oi_woff, i, m.oi_bits);
-    const uint32_t e = (i == (uint32_t)m.n_ids - 1) ? m.n_off : unpack_at(base + m.oi_woff, i + 1, m.oi_bits);
+    const BlockMeta m = kw_load_block_meta(ix.blk_meta + src.blk_base + b);
+    const uint32_t* __restrict__ base = src.base;
+    uint32_t s, e;
+    if constexpr (KW_LIST_TABLE) {
+        const uint32_t* __restrict__ oi = base + m.oi_woff;
+        const bool last = i == (uint32_t)m.n_ids - 1;
+        uint32_t sh;
+        const unsigned long long two = kw_window_at(oi, i, m.oi_bits, sh);
+        const uint64_t mask = m.oi_bits >= 32 ? 0xFFFFFFFFull : ((1ull << m.oi_bits) - 1ull);
+        s = (uint32_t)((two >> sh) & mask);
+        uint32_t nx = (uint32_t)((two >> ((sh + m.oi_bits) & 63u)) & mask);
+        if (m.oi_bits > 16) nx = unpack_at_nb(oi, last ? i : i + 1, m.oi_bits);
+        e = last ? m.n_off : nx;
+    } else {
+        s = unpack_at(base + m.oi_woff, i, m.oi_bits);
+        e = (i == (uint32_t)m.n_ids - 1) ? m.n_off : unpack_at(base + m.oi_woff, i + 1, m.oi_bits);
+    }
     TokRun r;
     r.w = base + m.off_woff;
     r.start = s;
@@ -548,42 +682,66 @@ __device__ inline TokRun load_run(const IndexView& ix, const ListDesc& d, uint32
     r.n = (e - s) - run_last_flag(r);
     return r;
 }
+__device__ inline TokRun load_run(const IndexView& ix, const ListDesc& d, uint32_t pos) { return load_run(ix, kw_run_src(ix, d), pos); }
 
 // load_run for ALL of a hit's tokens, level by level: descriptors, block metadata, the offset_index pair, the first offsets, the last-element
 // flag — each level's loads for every token are issued before any of them is waited for. Called token by token, hipcc emitted the chains one
 // after the other (`s_waitcnt vmcnt(0)` at each of a chain's five levels before the next token's first load): fifteen dependent memory round
 // trips per scored hit where five do; the score kernel spent 0.81 of its 1.38 ms there. Same values as load_run (the branch-free element fetch
 // reads the same two words; a width of 0 masks to 0).
-__device__ inline uint32_t unpack_at_nb(const uint32_t* __restrict__ w, uint32_t idx, uint32_t bits) {      // (guard word behind every packed array: tsgpu_format.h)
-    const uint64_t bitpos = (uint64_t)idx * bits;
-    const uint32_t* __restrict__ p = w + (bitpos >> 5);
-    const uint64_t two = (uint64_t)p[0] | ((uint64_t)p[1] << 32);
-    const uint64_t mask = bits >= 32 ? 0xFFFFFFFFull : ((1ull << bits) - 1ull);
-    return (uint32_t)((two >> (uint32_t)(bitpos & 31)) & mask);
-}
-template <int TMAX>
-__device__ inline void load_runs_staged(const IndexView& ix, const KwQueryDev& q, const uint32_t (&pos)[TMAX], uint32_t T, TokRun (&runs)[TMAX], uint32_t& off_words) {
+// src(k) = the KwRunSrc of the query's token k: from the descriptors (one more level of loads in front of the chain) or from the work item's list table
+// (kw_score_kernel: no load at all). Per token and hit: two 16-byte BlockMeta loads, one offset_index window, one offsets window, and the run's last
+// element where the offsets window does not hold it.
+template <int TMAX, class SrcFn>
+__device__ inline void load_runs_staged_from(const IndexView& ix, SrcFn src, const uint32_t (&pos)[TMAX], uint32_t T, TokRun (&runs)[TMAX], uint32_t& off_words) {
     const uint32_t* base[TMAX];
     uint32_t blk[TMAX];
     bool on[TMAX];
 #pragma unroll
     for (int t = 0; t < TMAX; t++) {
         on[t] = (uint32_t)t < T && (t == 0 || T > 1);
-        const ListDesc& d = ix.lists[q.list[on[t] ? t : 0]];
-        base[t] = ix.payload + d.payload_base;
+        const KwRunSrc d = src(on[t] ? (uint32_t)t : 0u);
+        base[t] = d.base;
         blk[t] = d.blk_base + (pos[on[t] ? t : 0] >> 8);
     }
     BlockMeta m[TMAX];
 #pragma unroll
-    for (int t = 0; t < TMAX; t++) m[t] = ix.blk_meta[blk[t]];
+    for (int t = 0; t < TMAX; t++) m[t] = kw_load_block_meta(ix.blk_meta + blk[t]);
     uint32_t s[TMAX], e[TMAX];
+    if constexpr (KW_LIST_TABLE) {
+        unsigned long long two[TMAX];
+        uint32_t sh[TMAX], nxw[TMAX];
+        bool wide = false;
 #pragma unroll
-    for (int t = 0; t < TMAX; t++) {
-        const uint32_t i = pos[on[t] ? t : 0] & 255;
-        const uint32_t* __restrict__ oi = base[t] + m[t].oi_woff;
-        s[t] = unpack_at_nb(oi, i, m[t].oi_bits);
-        const uint32_t nx = unpack_at_nb(oi, i + 1 < (uint32_t)m[t].n_ids ? i + 1 : i, m[t].oi_bits);
-        e[t] = (i == (uint32_t)m[t].n_ids - 1) ? m[t].n_off : nx;
+        for (int t = 0; t < TMAX; t++) {
+            two[t] = kw_window_at(base[t] + m[t].oi_woff, pos[on[t] ? t : 0] & 255, m[t].oi_bits, sh[t]);
+            wide = wide || m[t].oi_bits > 16;
+            nxw[t] = 0;
+        }
+        if (wide) {                                       // (a block of more than 65 535 offsets: elements i and i + 1 may not share a window)
+#pragma unroll
+            for (int t = 0; t < TMAX; t++) {
+                const uint32_t i = pos[on[t] ? t : 0] & 255;
+                nxw[t] = unpack_at_nb(base[t] + m[t].oi_woff, i + 1 < (uint32_t)m[t].n_ids ? i + 1 : i, m[t].oi_bits);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < TMAX; t++) {
+            const uint32_t i = pos[on[t] ? t : 0] & 255;
+            const uint64_t mask = m[t].oi_bits >= 32 ? 0xFFFFFFFFull : ((1ull << m[t].oi_bits) - 1ull);
+            s[t] = (uint32_t)((two[t] >> sh[t]) & mask);
+            const uint32_t nx = m[t].oi_bits > 16 ? nxw[t] : (uint32_t)((two[t] >> ((sh[t] + m[t].oi_bits) & 63u)) & mask);
+            e[t] = (i == (uint32_t)m[t].n_ids - 1) ? m[t].n_off : nx;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < TMAX; t++) {
+            const uint32_t i = pos[on[t] ? t : 0] & 255;
+            const uint32_t* __restrict__ oi = base[t] + m[t].oi_woff;
+            s[t] = unpack_at_nb(oi, i, m[t].oi_bits);
+            const uint32_t nx = unpack_at_nb(oi, i + 1 < (uint32_t)m[t].n_ids ? i + 1 : i, m[t].oi_bits);
+            e[t] = (i == (uint32_t)m[t].n_ids - 1) ? m[t].n_off : nx;
+        }
     }
     uint64_t x[TMAX];
 #pragma unroll
@@ -624,6 +782,10 @@ __device__ inline void load_runs_staged(const IndexView& ix, const KwQueryDev& q
             off_words += run_raw_len(runs[t]) + 1;
         } else { TokRun r; r.w = nullptr; r.start = 0; r.n = 0; r.base = 0; r.raw_len = 0; r.meta = 0; r.c01 = 0; runs[t] = r; }      // (= empty_run())
     }
+}
+template <int TMAX>
+__device__ inline void load_runs_staged(const IndexView& ix, const KwQueryDev& q, const uint32_t (&pos)[TMAX], uint32_t T, TokRun (&runs)[TMAX], uint32_t& off_words) {
+    load_runs_staged_from<TMAX>(ix, [&](uint32_t k) { return kw_run_src(ix, ix.lists[q.list[k]]); }, pos, T, runs, off_words);
 }
 
 // The same for N (list, posting position) SLOTS of one hit — the multi-field score kernel's form (round 6): a hit of a query over two query_by fields holds up
@@ -1100,16 +1262,19 @@ __device__ inline ScoredHit sort_scores(const IndexView& ix, const KwQueryDev& q
 
 // score_results2 + compute_aggregated_score + compute_sort_scores for ONE query_by field (plain string); pos[t] = posting
 // position of found token t
-template <int TMAX, bool KEYS = true>
-__device__ inline ScoredHit score_hit(const IndexView& ix, const KwQueryDev& q, uint32_t seq_id, const uint32_t (&pos)[TMAX]) {
+// TAB: tab = the work item's list table (kw_score_kernel): one KwRunRow per token of the query instead of a descriptor load per token and hit
+template <int TMAX, bool KEYS = true, bool TAB = false>
+__device__ inline ScoredHit score_hit(const IndexView& ix, const KwQueryDev& q, uint32_t seq_id, const uint32_t (&pos)[TMAX], const KwRunRow* tab = nullptr) {
     const uint32_t T = q.n_lists;
     uint32_t off_words = 0;
     TokRun runs[TMAX];
-    if constexpr (TMAX <= 3) load_runs_staged<TMAX>(ix, q, pos, T, runs, off_words);
+    if constexpr (TMAX <= 3 && TAB) load_runs_staged_from<TMAX>(ix, [&](uint32_t k) { return kw_run_src(ix, tab + k); }, pos, T, runs, off_words);
+    else if constexpr (TMAX <= 3) load_runs_staged<TMAX>(ix, q, pos, T, runs, off_words);
     else {
 #pragma unroll
         for (int t = 0; t < TMAX; t++) {
-            if ((uint32_t)t < T && (t == 0 || T > 1)) { runs[t] = load_run(ix, ix.lists[q.list[t]], pos[t]); off_words += run_raw_len(runs[t]) + 1; }
+            if constexpr (TAB) { if ((uint32_t)t < T && (t == 0 || T > 1)) { runs[t] = load_run(ix, kw_run_src(ix, tab + t), pos[t]); off_words += run_raw_len(runs[t]) + 1; } else runs[t] = empty_run(); }
+            else if ((uint32_t)t < T && (t == 0 || T > 1)) { runs[t] = load_run(ix, ix.lists[q.list[t]], pos[t]); off_words += run_raw_len(runs[t]) + 1; }
             else runs[t] = empty_run();
         }
     }
@@ -1321,7 +1486,7 @@ struct KwSmem {
 // VQ: some query of the launch has a TSGPU_SORT_VECTOR_QUERY slot (the host knows): only those launches carry the wave-cooperative distance code (kw_vq_sort.hip.h).
 template <int TMAX, int CAP, bool MF, bool S2, bool SCORE, bool PLAIN = false, bool VQ = false>
 __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& sm, const IndexView& ix, const KwQueryDev& q, uint32_t n_take,
-                                      const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out, uint32_t ids_out_base) {
+                                      const uint32_t* __restrict__ aux_ids, uint32_t* __restrict__ ids_out, uint32_t ids_out_base, const KwRunRow* tab = nullptr) {
     // make room: at most n_take (<=256) new entries. (The score kernel decides AFTER scoring, from the number of hits that beat the
     // current k-th best — see below; in the fused kernel that would keep the scores live across the sort and cost it a workgroup per CU.)
     if constexpr (!SCORE) { if (sm.tk_cnt + KW_THREADS > (uint32_t)CAP) topk_compact<CAP, S2>(sm.tk, &sm.tk_cnt, q.k, sm.thr, &sm.have_thr); }
@@ -1359,7 +1524,7 @@ __device__ inline void kw_score_stage(KwSmem<TMAX, CAP, MF, S2, false, SCORE>& s
 #if defined(TSGPU_EXP) && TSGPU_EXP == 6
                 h.s0 = (int64_t)(seq_id * 2654435761u); h.s1 = (int64_t)pos[0] + pos[TMAX - 1]; h.s2 = 0; h.text_match = h.s0; h.off_words = 1;
 #else
-                h = score_hit<TMAX, !PLAIN>(ix, q, seq_id, pos);
+                h = score_hit<TMAX, !PLAIN, SCORE && KW_LIST_TABLE>(ix, q, seq_id, pos, tab);      // (the score kernel hands its list table; the fused kernel has none)
 #endif
             }
         }
@@ -1920,6 +2085,7 @@ __device__ __forceinline__ void kw_score_body(const IndexView& ix, const KwQuery
                                               const uint32_t* __restrict__ hits_all, const uint64_t* __restrict__ hit_off, const uint32_t bid) {
     __shared__ KwSmem<TMAX, CAP, MF, S2, false, true> sm;
     __shared__ KwQueryDev sq;
+    __shared__ KwRunRow tab[(KW_LIST_TABLE && !MF) ? TMAX : 1];          // the list table (single-field launches): a row per token of the query
     constexpr int NP = decltype(sm)::NP;          // posting positions per record: TMAX, or TMAX x KW_MAX_FIELDS for several query_by fields
     const uint32_t t = threadIdx.x;
     const KwWorkItem wi = work[bid];
@@ -1927,6 +2093,18 @@ __device__ __forceinline__ void kw_score_body(const IndexView& ix, const KwQuery
         const uint32_t* src = (const uint32_t*)(queries + (wi.query & 0x0FFFFFFFu));      // (multi-field items carry the driver field in the top bits)
         uint32_t* dst = (uint32_t*)&sq;
         for (uint32_t i = t; i < sizeof(KwQueryDev) / 4; i += KW_THREADS) dst[i] = src[i];
+    }
+    if constexpr (KW_LIST_TABLE && !MF) {
+        // lane k of the second wave fills token k's row from the query in global memory (the copy above is not visible before the barrier); rows behind
+        // the query's last token repeat token 0's, which is what the staged loader reads for an absent token
+        if (t >= 64 && t < 64 + (uint32_t)TMAX) {
+            const KwQueryDev* __restrict__ gq = queries + (wi.query & 0x0FFFFFFFu);
+            const uint32_t k = t - 64;
+            const uint32_t n = gq->n_lists;
+            KwRunRow r; r.payload_lo = r.payload_hi = r.blk_base = r.pad = 0;                  // (a query without a token has no hit to score)
+            if (n) r = kw_run_row(ix.lists[gq->list[k < n ? k : 0u]]);
+            tab[k] = r;
+        }
     }
     if (t == 0) {
         sm.q1_cnt = 0; sm.qf_cnt = 0; sm.tk_cnt = 0; sm.have_thr = 0; sm.n_match = 0; sm.n_emit = 0; sm.off_words = 0;
@@ -1953,7 +2131,7 @@ __device__ __forceinline__ void kw_score_body(const IndexView& ix, const KwQuery
         }
         if (t == 0) sm.qf_cnt = n;
         __syncthreads();
-        kw_score_stage<TMAX, CAP, MF, S2, true, PLAIN, VQ>(sm, ix, q, n, aux_ids, my_ids_out, 0u);
+        kw_score_stage<TMAX, CAP, MF, S2, true, PLAIN, VQ>(sm, ix, q, n, aux_ids, my_ids_out, 0u, tab);
     }
     kw_write_partial(sm, q, part, bid);
 }

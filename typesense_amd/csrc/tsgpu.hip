@@ -1858,8 +1858,9 @@ int record_touched(tsgpu_ctx* ctx, KwLane& L, const Plan& P, bool dev_plan, cons
     tt.find_work_items = c[5]; tt.find_hit_records = c[6];
     tt.find_requested_bytes = c[0] + c[1] + c[2] + c[3] + c[4];
     // the score kernel's requests per hit record are fixed sizes (kw_score_kernel / load_runs_staged): the record itself, per token one
-    // BlockMeta (32 B), the offset_index pair (two 8-byte fetches) and the first offsets (8 B); per numeric sort key one column value; the
-    // rare third.. occurrence of a token in a document (one more 8-byte fetch each) is not counted
+    // BlockMeta (32 B), the offset_index pair (one 8-byte window; TSGPU_LIST_TABLE=0: two) and the first offsets (8 B); per numeric sort key one column
+    // value; the rare third.. occurrence of a token in a document and the second window of an offset_index wider than 16 bits (one more 8-byte fetch
+    // each) are not counted
     uint64_t sb = 0;
     std::vector<uint64_t> nm_host;
     if (nm_dev) {                                            // (measurement only: one small read-back)
@@ -1867,7 +1868,7 @@ int record_touched(tsgpu_ctx* ctx, KwLane& L, const Plan& P, bool dev_plan, cons
         if (hipMemcpy(nm_host.data(), nm_dev, (size_t)n_queries * 8, hipMemcpyDeviceToHost) == hipSuccess) nm = nm_host.data();
     }
     for (uint32_t i = 0; nm && !dev_plan && i < n_queries; i++)
-        sb += nm[i] * (4ull * ((P.q[i].n_lists <= 3 ? 3 : KW_MAX_TOKENS) + 1) + 56ull * P.q[i].n_lists + 8ull * n_column_sort_keys(P, dev_plan, queries, i));
+        sb += nm[i] * (4ull * ((P.q[i].n_lists <= 3 ? 3 : KW_MAX_TOKENS) + 1) + (KW_LIST_TABLE ? 48ull : 56ull) * P.q[i].n_lists +8ull * n_column_sort_keys(P, dev_plan, queries, i));
     tt.score_requested_bytes = sb;
     return TSGPU_OK;
 }

@@ -76,7 +76,9 @@ static const uint32_t LIST_HAS_BREAKS = 1u;
 //   {pos, bits}: bits = which of the ids [32w, 32w + 32) the list holds; pos = posting position (block * 256 + slot) of the lowest one.
 // "Is id x in the list, and where?" — what every probe of the third.. lists asks (posting_list_t::iterator_t::skip_to + the equality test of
 // or_iterator_t::intersect, /root/reference/src/or_iterator.cpp:20-79) — is ONE load: bit x & 31 of entry x >> 5, position = pos + popcount of
-// the lower bits. The ids of one entry are consecutive posting positions also where they straddle two blocks, as long as the block in front of
+// the lower bits. (One load of the DIRECTORY: a probe through ix.lists[handle] also reads the descriptor's first_id, last_id and dir_slot first —
+// three more dependent loads, and the entry's two words as two loads — unless the caller holds those constants: the find kernel's list table,
+// KwProbeRow in kw_kernels.hip.h, is the form that costs one 8-byte load per probe.) The ids of one entry are consecutive posting positions also where they straddle two blocks, as long as the block in front of
 // the boundary is FULL: its last slot is position b * 256 + 255, the next block's slot 0 is (b + 1) * 256. Only an entry that straddles a boundary
 // behind a PART-FILLED block (incremental commits leave those; a freshly packed list has none but its last block) carries IDDIR_SPLIT in pos:
 // a probe that finds its bit set there, and ids beyond the pool's range, take the regular two-level search. (Marking every boundary — one entry
